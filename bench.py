@@ -14,6 +14,12 @@ Shards are expressed as :class:`LocalShard` (explicit TensorSlice layouts),
 so the bench needs no process group: ranks coordinate through a TCPStore
 (barriers + max-reduce).  torchrun only supplies the env.
 
+A plain run sets up, warms up, times ``--steps`` steps and prints the JSON
+result line.  ``--full`` additionally runs the bit-exact correctness probe on
+the pulled weights between warmup and the timed steps.  ``--dump-outputs DIR``
+writes what the last timed step pulled (a fixed, seeded sample of every
+entry) as ``DIR/<name>.npy`` so two builds can be compared output for output.
+
 Single GPU:      python bench.py --steps 5 --warmup 2
 N GPUs (driver): python -m torch.distributed.run --nnodes=1 --nproc-per-node N \
                      --master-addr 127.0.0.1 bench.py --gpus N --steps K --warmup W
@@ -30,6 +36,38 @@ import time
 import torch
 
 from torchstore_amd.runtime import Actor, endpoint
+
+
+DUMP_SEED = 20240531
+DUMP_MAX_ELEMS = 32768  # per entry: 291 entries x 128 KiB fp32 = 36 MiB at most
+
+
+def dump_state_dict(sd, out_dir, prefix=""):
+    """Write a fixed, seeded sample of every entry's local tensor as float32
+    ``out_dir/<prefix><name>.npy``.  Entries up to DUMP_MAX_ELEMS elements are
+    written whole; larger ones at DUMP_MAX_ELEMS flat positions drawn from a
+    generator seeded by (DUMP_SEED, entry index), identical from run to run."""
+    import numpy as np
+
+    from torchstore_amd.types import LocalShard
+
+    os.makedirs(out_dir, exist_ok=True)
+    for i, (name, v) in enumerate(sd.items()):
+        local = v.tensor if isinstance(v, LocalShard) else v
+        flat = local.reshape(-1)
+        if flat.numel() > DUMP_MAX_ELEMS:
+            g = torch.Generator(device="cpu")
+            g.manual_seed(DUMP_SEED + i)
+            idx = torch.randint(
+                0, flat.numel(), (DUMP_MAX_ELEMS,), generator=g,
+                dtype=torch.int64,
+            )
+            flat = flat[idx.to(flat.device)]
+        arr = flat.to(torch.float32).cpu().numpy()
+        np.save(
+            os.path.join(out_dir, prefix + name.replace("/", "_") + ".npy"),
+            arr,
+        )
 
 
 class GeneratorActor(Actor):
@@ -58,6 +96,11 @@ class GeneratorActor(Actor):
         torch.cuda.synchronize()
         nbytes = sum(op.nbytes for op in self.dest._plan)
         return time.perf_counter() - t0, nbytes
+
+    @endpoint
+    def dump_outputs(self, out_dir, prefix):
+        dump_state_dict(self.dst_sd, out_dir, prefix)
+        torch.cuda.synchronize()
 
     @endpoint
     def verify_pattern(self):
@@ -92,6 +135,12 @@ def parse_args():
                    help="override layer count (debug only; invalidates the metric)")
     p.add_argument("--mode", choices=["state_dict", "direct"],
                    default="state_dict")
+    p.add_argument("--full", action="store_true",
+                   help="also run the bit-exact correctness probe on the "
+                        "pulled weights (outside the timed region)")
+    p.add_argument("--dump-outputs", metavar="DIR", default=None,
+                   help="after the timed steps, write what the last step "
+                        "pulled as DIR/<name>.npy (float32, seeded sample)")
     return p.parse_args()
 
 
@@ -222,16 +271,16 @@ async def run_bench(args, rank, world, local_rank, coord: Coord):
         await one_step()
     barrier()
 
-    # correctness guard (outside the timed region): every pulled shard must
-    # equal the position-determined pattern — this validates the cross-GPU
-    # (xGMI) read paths end to end, not just co-located regions
-    if args.mode == "direct":
+    # correctness guard (--full only, outside the timed region): every pulled
+    # shard must equal the position-determined pattern — this validates the
+    # cross-GPU (xGMI) read paths end to end, not just co-located regions
+    if args.full and args.mode == "direct":
         bad = await gen.verify_pattern.call_one()
         if bad:
             raise RuntimeError(
                 f"bench correctness probe failed (direct pull): {bad[:5]}"
             )
-    else:
+    elif args.full:
         bad = []
         for name, v in dst_sd.items():
             local = v.tensor if isinstance(v, LocalShard) else v
@@ -257,6 +306,14 @@ async def run_bench(args, rank, world, local_rank, coord: Coord):
         await one_step()
     barrier()
     elapsed = time.perf_counter() - t0
+
+    if args.dump_outputs:
+        prefix = f"rank{rank}." if world > 1 else ""
+        out_dir = os.path.abspath(args.dump_outputs)
+        if args.mode == "direct":
+            await gen.dump_outputs.call_one(out_dir, prefix)
+        else:
+            dump_state_dict(dst_sd, out_dir, prefix)
 
     # per-rank phase breakdown (stderr): makes a bad SCALE curve diagnosable
     import sys as _sys

@@ -94,3 +94,41 @@ async def test_bench_flow_2rank_cpu():
             await mesh.stop()
         await ts.shutdown()
         await close_connections()
+
+
+def test_bench_dump_outputs_deterministic(tmp_path):
+    """bench.py --dump-outputs: small entries are written whole, large ones
+    as a seeded sample that is identical from run to run, all float32."""
+    import importlib.util
+    from pathlib import Path
+
+    import numpy as np
+
+    spec = importlib.util.spec_from_file_location(
+        "_bench_under_test", Path(__file__).resolve().parent.parent / "bench.py"
+    )
+    bench = importlib.util.module_from_spec(spec)
+    spec.loader.exec_module(bench)
+
+    big = torch.arange(
+        2 * bench.DUMP_MAX_ELEMS, dtype=torch.float32
+    ).reshape(2, -1)
+    sd = {
+        "small.weight": torch.arange(12, dtype=torch.bfloat16).reshape(3, 4),
+        "big.weight": big,
+    }
+    a, b = tmp_path / "a", tmp_path / "b"
+    bench.dump_state_dict(sd, str(a))
+    bench.dump_state_dict(sd, str(b), prefix="rank1.")
+
+    small = np.load(a / "small.weight.npy")
+    assert small.dtype == np.float32
+    assert np.array_equal(small, np.arange(12, dtype=np.float32))
+
+    sample = np.load(a / "big.weight.npy")
+    assert sample.dtype == np.float32
+    assert sample.shape == (bench.DUMP_MAX_ELEMS,)
+    # values are their own flat index: every sample is a real element
+    assert sample.min() >= 0 and sample.max() < big.numel()
+    assert len(np.unique(sample)) > bench.DUMP_MAX_ELEMS // 2
+    assert np.array_equal(sample, np.load(b / "rank1.big.weight.npy"))
