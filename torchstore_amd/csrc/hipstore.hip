@@ -14,6 +14,9 @@
 //     strided->strided), replacing per-slice torch copies in reshard
 //     pack/unpack (reference hot loops: storage_volume.py:220-277,
 //     utils.py:199-212, direct_weight_sync.py:350).
+//     A launch whose slices are all contiguous 16B-aligned ranges (every
+//     launch of the 1-GPU state_dict put/get) takes copy_flat_kernel, a
+//     block-per-unit streaming copy, instead of the general kernel.
 //   * cast_copy — K3: fused dtype cast + pack (f32<->bf16/f16), one HBM
 //     read + one write, vectorized 16B/lane (reference:
 //     state_dict_utils.py:177-189 casts every floating param per sync).
@@ -30,6 +33,7 @@
 #include <pybind11/stl.h>
 
 #include <algorithm>
+#include <atomic>
 #include <cstdint>
 #include <cstring>
 #include <mutex>
@@ -57,17 +61,29 @@ namespace py = pybind11;
 
 static constexpr int kStreamsPerDevice = 8;
 
-struct DevicePool {
-  std::vector<hipStream_t> streams;
-  // pinned host staging for slice descriptors + device copy of them
+// descriptor ring depth = the state_dict pipeline depth (8 concurrent
+// sub-batch RPCs): a launch waits only for the kernel that last used ITS
+// slot, so up to 8 launches queue on a stream behind a running kernel
+static constexpr int kDescSlots = 8;
+
+// one descriptor staging slot: pinned host buffer + device copy of it
+struct DescSlot {
+  std::mutex mu;  // held while the slot is waited on, filled and enqueued
   void* h_desc = nullptr;
   void* d_desc = nullptr;
-  size_t desc_cap = 0;
-  // guards h_desc reuse: recorded after each staging H2D enqueue
-  hipEvent_t desc_evt = nullptr;
+  size_t cap = 0;
+  // guards buffer reuse: recorded after the kernel that reads d_desc
+  hipEvent_t evt = nullptr;
+};
+
+struct DevicePool {
+  std::vector<hipStream_t> streams;
+  DescSlot slots[kDescSlots];
+  uint64_t next_slot = 0;  // under g_mutex
 };
 
 static std::mutex g_mutex;
+// node-based map: DevicePool (mutexes inside) is never moved once built
 static std::unordered_map<int, DevicePool> g_pools;
 
 static DevicePool& pool_for(int device) {
@@ -75,23 +91,28 @@ static DevicePool& pool_for(int device) {
   auto it = g_pools.find(device);
   if (it != g_pools.end()) return it->second;
   HIP_CHECK(hipSetDevice(device));
-  DevicePool p;
-  p.streams.resize(kStreamsPerDevice);
+  std::vector<hipStream_t> streams(kStreamsPerDevice);
   for (int i = 0; i < kStreamsPerDevice; ++i) {
-    HIP_CHECK(hipStreamCreateWithFlags(&p.streams[i], hipStreamNonBlocking));
+    HIP_CHECK(hipStreamCreateWithFlags(&streams[i], hipStreamNonBlocking));
   }
-  return g_pools.emplace(device, std::move(p)).first->second;
+  DevicePool& p = g_pools[device];
+  p.streams = std::move(streams);
+  return p;
 }
 
-static void ensure_desc_capacity(DevicePool& p, int device, size_t bytes) {
-  if (p.desc_cap >= bytes) return;
+// caller holds s.mu and has already waited on s.evt, so no kernel still
+// reads the buffers that are freed here
+static void ensure_desc_capacity(DescSlot& s, int device, size_t bytes) {
+  if (s.cap >= bytes) return;
   size_t cap = bytes * 2 + 4096;
   HIP_CHECK(hipSetDevice(device));
-  if (p.h_desc) HIP_CHECK(hipHostFree(p.h_desc));
-  if (p.d_desc) HIP_CHECK(hipFree(p.d_desc));
-  HIP_CHECK(hipHostMalloc(&p.h_desc, cap, hipHostMallocDefault));
-  HIP_CHECK(hipMalloc(&p.d_desc, cap));
-  p.desc_cap = cap;
+  if (s.h_desc) HIP_CHECK(hipHostFree(s.h_desc));
+  if (s.d_desc) HIP_CHECK(hipFree(s.d_desc));
+  s.h_desc = s.d_desc = nullptr;
+  s.cap = 0;
+  HIP_CHECK(hipHostMalloc(&s.h_desc, cap, hipHostMallocDefault));
+  HIP_CHECK(hipMalloc(&s.d_desc, cap));
+  s.cap = cap;
 }
 
 // ---------------------------------------------------------------------------
@@ -245,11 +266,12 @@ static uint32_t pick_tile(uint64_t total_bytes) {
   return total_bytes > (512ull << 20) ? 32768u : 16384u;
 }
 
-// grid cap for the slice kernel (blocks); HIPSTORE_GRID overrides
-static uint32_t pick_grid_cap() {
+// grid cap for the copy kernels (blocks); HIPSTORE_GRID overrides the
+// kernel's own default
+static uint32_t pick_grid_cap(uint32_t dflt) {
   const char* e = getenv("HIPSTORE_GRID");
   uint32_t forced = e ? (uint32_t)atoi(e) : 0u;
-  return forced >= 64 ? forced : 8192u;
+  return forced >= 64 ? forced : dflt;
 }
 
 // row-packed units span this many bytes of small rows regardless of the
@@ -512,39 +534,212 @@ static bool use_nt_stores() {
   return e ? atoi(e) != 0 : true;
 }
 
-// upload descriptors through the pinned staging buffer + launch the kernel
+// ---------------------------------------------------------------------------
+// flat streaming copy — every slice of the launch is one contiguous,
+// 16B-aligned byte range (the 1-GPU state_dict put and get are entirely this)
+// ---------------------------------------------------------------------------
+//
+// Unit = one `span`-byte piece of one copy.  The WHOLE 256-thread block
+// works on one unit (each load/store instruction of the block covers 4 KiB
+// contiguous) and blocks take units interleaved (blockIdx.x + k*gridDim.x),
+// so the resident grid sweeps one compact, advancing window of the buffers
+// instead of one private stream per wave.  The descriptor lookup depends on
+// blockIdx only, i.e. it is uniform over the block.
+
+struct FlatDesc {
+  uintptr_t src;
+  uintptr_t dst;
+  uint64_t nbytes;        // multiple of 16, > 0
+  uint64_t units_prefix;  // exclusive prefix sum of units
+};
+static_assert(sizeof(FlatDesc) == 32, "FlatDesc is meant to be 32 bytes");
+
+// defaults from the span x grid x NT sweep (profiles/flat_copy_ab.log):
+// 16 KiB units won every pattern; the Llama-shaped 2 GB sub-batch kept
+// gaining up to a 65536-block cap (~2 units per block; 5.94 TB/s vs 5.61 at
+// the 2048 that usually suits memory-bound kernels); non-temporal LOADS add
+// 3-4% on top of non-temporal stores (HIPSTORE_FLAT_NTLOAD=0 turns them off)
+static constexpr uint32_t kFlatSpanDefault = 16384u;
+static constexpr uint32_t kFlatGridDefault = 65536u;
+
+// unit span of the flat kernel; HIPSTORE_FLAT_SPAN overrides (multiple of
+// 4 KiB so every unit start keeps the 16B alignment and whole-block rows)
+static uint32_t pick_flat_span() {
+  const char* e = getenv("HIPSTORE_FLAT_SPAN");
+  uint32_t forced = e ? (uint32_t)atoi(e) : 0u;
+  if (forced >= 4096 && forced <= (1u << 24) && (forced & 4095u) == 0)
+    return forced;
+  return kFlatSpanDefault;
+}
+
+static bool use_flat_kernel() {
+  const char* e = getenv("HIPSTORE_FLAT");
+  return e ? atoi(e) != 0 : true;
+}
+
+typedef uint32_t flat_v4u __attribute__((ext_vector_type(4)));
+// the addresses arrive as integers; naming the global address space lets
+// the compiler emit global_load/global_store instead of generic flat ops
+typedef __attribute__((address_space(1))) flat_v4u flat_gv4u;
+
+template <bool NT>
+__device__ __forceinline__ void flat_store(flat_gv4u* p, flat_v4u v) {
+  if (NT) __builtin_nontemporal_store(v, p); else *p = v;
+}
+
+template <bool NTL>
+__device__ __forceinline__ flat_v4u flat_load(const flat_gv4u* p) {
+  return NTL ? __builtin_nontemporal_load(p) : *p;
+}
+
+template <bool NT, bool NTL>
+__global__ void __launch_bounds__(256)
+copy_flat_kernel(const FlatDesc* __restrict__ descs, uint32_t ndescs,
+                 uint64_t total_units, uint32_t span) {
+  uint32_t lo = 0;  // units only grow, so the search never moves back
+  FlatDesc d = {};
+  uint64_t next_prefix = 0;  // forces the lookup on the first unit
+  for (uint64_t unit = blockIdx.x; unit < total_units; unit += gridDim.x) {
+    if (unit >= next_prefix) {
+      // left the current copy: greatest s with prefix <= unit.  Big copies
+      // span many strides of the grid, so most units skip this and start
+      // their loads without a dependent descriptor read in front
+      uint32_t hi = ndescs - 1;
+      while (lo < hi) {
+        uint32_t mid = (lo + hi + 1) >> 1;
+        if (descs[mid].units_prefix <= unit) lo = mid; else hi = mid - 1;
+      }
+      d = descs[lo];
+      next_prefix = (lo + 1 < ndescs) ? descs[lo + 1].units_prefix : ~0ull;
+    }
+    const uint64_t off = (unit - d.units_prefix) * span;
+    const uint64_t rem = d.nbytes - off;
+    const uint32_t n4 = (uint32_t)(rem < span ? rem : span) >> 4;
+    const flat_gv4u* s4 = reinterpret_cast<const flat_gv4u*>(d.src + off);
+    flat_gv4u* d4 = reinterpret_cast<flat_gv4u*>(d.dst + off);
+    uint32_t i = threadIdx.x;
+    // x8: 128 B of loads in flight per lane before the first store
+    for (; i + 1792 < n4; i += 2048) {
+      flat_v4u v0 = flat_load<NTL>(s4 + i);
+      flat_v4u v1 = flat_load<NTL>(s4 + i + 256);
+      flat_v4u v2 = flat_load<NTL>(s4 + i + 512);
+      flat_v4u v3 = flat_load<NTL>(s4 + i + 768);
+      flat_v4u v4 = flat_load<NTL>(s4 + i + 1024);
+      flat_v4u v5 = flat_load<NTL>(s4 + i + 1280);
+      flat_v4u v6 = flat_load<NTL>(s4 + i + 1536);
+      flat_v4u v7 = flat_load<NTL>(s4 + i + 1792);
+      flat_store<NT>(d4 + i, v0);
+      flat_store<NT>(d4 + i + 256, v1);
+      flat_store<NT>(d4 + i + 512, v2);
+      flat_store<NT>(d4 + i + 768, v3);
+      flat_store<NT>(d4 + i + 1024, v4);
+      flat_store<NT>(d4 + i + 1280, v5);
+      flat_store<NT>(d4 + i + 1536, v6);
+      flat_store<NT>(d4 + i + 1792, v7);
+    }
+    for (; i + 768 < n4; i += 1024) {
+      flat_v4u v0 = flat_load<NTL>(s4 + i);
+      flat_v4u v1 = flat_load<NTL>(s4 + i + 256);
+      flat_v4u v2 = flat_load<NTL>(s4 + i + 512);
+      flat_v4u v3 = flat_load<NTL>(s4 + i + 768);
+      flat_store<NT>(d4 + i, v0);
+      flat_store<NT>(d4 + i + 256, v1);
+      flat_store<NT>(d4 + i + 512, v2);
+      flat_store<NT>(d4 + i + 768, v3);
+    }
+    for (; i < n4; i += 256) flat_store<NT>(d4 + i, flat_load<NTL>(s4 + i));
+  }
+}
+
+// launches that went to the flat kernel (tests tell the two paths apart)
+static std::atomic<uint64_t> g_flat_launches{0};
+
+// a launch is flat when every slice is one contiguous 16B-aligned range;
+// a single odd entry keeps the whole launch on copy_slices_kernel
+static bool build_flat_descs(const std::vector<SliceDesc>& descs,
+                             uint32_t span, std::vector<FlatDesc>& out,
+                             uint64_t& units) {
+  out.clear();
+  out.reserve(descs.size());
+  units = 0;
+  for (const SliceDesc& d : descs) {
+    if (d.rows != 1 || d.ndim != 0 || d.rows_per_unit > 1) return false;
+    if (((d.src | d.dst | (uintptr_t)d.row_bytes) & 15u) != 0) return false;
+    if (d.row_bytes == 0) continue;
+    out.push_back(FlatDesc{d.src, d.dst, d.row_bytes, units});
+    units += ((uint64_t)d.row_bytes + span - 1) / span;
+  }
+  return true;
+}
+
+// upload descriptors through a ring slot's pinned staging buffer + launch
 static void launch_slice_descs(std::vector<SliceDesc>& descs, uint64_t units,
                                int device, hipStream_t stream,
                                uint32_t tile, bool remote = false) {
   if (units == 0 || descs.empty()) return;
+  std::vector<FlatDesc> flat;
+  uint64_t flat_units = 0;
+  uint32_t span = 0;
+  bool is_flat = false;
+  if (!remote && use_flat_kernel()) {
+    span = pick_flat_span();
+    is_flat = build_flat_descs(descs, span, flat, flat_units);
+    if (is_flat && flat_units == 0) return;  // nothing but empty copies
+  }
+  const void* payload = is_flat ? (const void*)flat.data()
+                                : (const void*)descs.data();
+  size_t bytes = is_flat ? flat.size() * sizeof(FlatDesc)
+                         : descs.size() * sizeof(SliceDesc);
+
   DevicePool& p = pool_for(device);
   HIP_CHECK(hipSetDevice(device));
-  size_t bytes = descs.size() * sizeof(SliceDesc);
-  std::lock_guard<std::mutex> lock(g_mutex);
-  ensure_desc_capacity(p, device, bytes);
-  if (p.desc_evt == nullptr) {
-    HIP_CHECK(hipEventCreateWithFlags(&p.desc_evt, hipEventDisableTiming));
-  } else {
-    // the previous call's KERNEL must be done before h_desc/d_desc are
-    // reused (calls may target different streams)
-    HIP_CHECK(hipEventSynchronize(p.desc_evt));
+  DescSlot* slot;
+  {
+    std::lock_guard<std::mutex> lock(g_mutex);
+    slot = &p.slots[p.next_slot++ % kDescSlots];
   }
-  std::memcpy(p.h_desc, descs.data(), bytes);
-  HIP_CHECK(hipMemcpyAsync(p.d_desc, p.h_desc, bytes, hipMemcpyHostToDevice,
-                           stream));
-  // memory-bound: cap the grid and chunk units over it (guide G11);
-  // each block consumes 4 contiguous unit ranges (one per wave)
-  uint32_t grid = (uint32_t)std::min<uint64_t>((units + 3) / 4, pick_grid_cap());
-  auto kern = use_nt_stores()
-                  ? (remote ? copy_slices_kernel<true, true>
-                            : copy_slices_kernel<true, false>)
-                  : (remote ? copy_slices_kernel<false, true>
-                            : copy_slices_kernel<false, false>);
-  hipLaunchKernelGGL(kern, dim3(grid), dim3(256), 0, stream,
-                     reinterpret_cast<const SliceDesc*>(p.d_desc),
-                     (uint32_t)descs.size(), units, tile);
+  std::lock_guard<std::mutex> slot_lock(slot->mu);
+  if (slot->evt == nullptr) {
+    HIP_CHECK(hipEventCreateWithFlags(&slot->evt, hipEventDisableTiming));
+  } else {
+    // only the KERNEL that last read this slot must be done before its
+    // buffers are reused or regrown; other slots' kernels keep running
+    HIP_CHECK(hipEventSynchronize(slot->evt));
+  }
+  ensure_desc_capacity(*slot, device, bytes);
+  std::memcpy(slot->h_desc, payload, bytes);
+  HIP_CHECK(hipMemcpyAsync(slot->d_desc, slot->h_desc, bytes,
+                           hipMemcpyHostToDevice, stream));
+  const bool nt = use_nt_stores();
+  if (is_flat) {
+    // one block per unit, interleaved; memory-bound, so cap the grid
+    uint32_t grid = (uint32_t)std::min<uint64_t>(
+        flat_units, pick_grid_cap(kFlatGridDefault));
+    const char* ntl_e = getenv("HIPSTORE_FLAT_NTLOAD");
+    const bool ntl = ntl_e ? atoi(ntl_e) != 0 : true;
+    auto kern = nt ? (ntl ? copy_flat_kernel<true, true>
+                          : copy_flat_kernel<true, false>)
+                   : (ntl ? copy_flat_kernel<false, true>
+                          : copy_flat_kernel<false, false>);
+    hipLaunchKernelGGL(kern, dim3(grid), dim3(256), 0, stream,
+                       reinterpret_cast<const FlatDesc*>(slot->d_desc),
+                       (uint32_t)flat.size(), flat_units, span);
+    g_flat_launches.fetch_add(1, std::memory_order_relaxed);
+  } else {
+    // memory-bound: cap the grid and chunk units over it (guide G11);
+    // each block consumes 4 contiguous unit ranges (one per wave)
+    uint32_t grid = (uint32_t)std::min<uint64_t>((units + 3) / 4,
+                                                 pick_grid_cap(8192u));
+    auto kern = nt ? (remote ? copy_slices_kernel<true, true>
+                             : copy_slices_kernel<true, false>)
+                   : (remote ? copy_slices_kernel<false, true>
+                             : copy_slices_kernel<false, false>);
+    hipLaunchKernelGGL(kern, dim3(grid), dim3(256), 0, stream,
+                       reinterpret_cast<const SliceDesc*>(slot->d_desc),
+                       (uint32_t)descs.size(), units, tile);
+  }
   HIP_CHECK(hipGetLastError());
-  HIP_CHECK(hipEventRecord(p.desc_evt, stream));
+  HIP_CHECK(hipEventRecord(slot->evt, stream));
 }
 
 // trivial desc for a flat byte copy (used by copy_batch's same-device path)
@@ -851,5 +1046,11 @@ PYBIND11_MODULE(_hipstore, m) {
   m.def("host_register", &host_register);
   m.def("host_unregister", &host_unregister);
   m.def("device_count", &device_count);
+  // flat-kernel defaults and launch counter, for the tests and A/B runs
+  m.attr("FLAT_SPAN_DEFAULT") = kFlatSpanDefault;
+  m.attr("DESC_RING_SLOTS") = kDescSlots;
+  m.def("flat_launches", []() {
+    return g_flat_launches.load(std::memory_order_relaxed);
+  });
   m.def("sync_device", &sync_device);
 }
