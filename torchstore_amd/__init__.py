@@ -8,7 +8,7 @@ resharding, state_dict exchange and zero-copy direct weight sync, built on:
   POSIX shared memory with pinned HIP copy streams (same host), RCCL
   send/recv (cross-host GPU), payload-in-RPC fallback;
 * hand-written CDNA4 (gfx950) HIP kernels for slice gather / scatter
-  assembly / fused dtype cast;
+  assembly / fused dtype cast / block-scaled FP8 quantisation;
 * GPU-resident storage volumes sized for 288 GB HBM3E per MI355X.
 
 Capability parity target: meta-pytorch/torchstore.
@@ -32,7 +32,9 @@ from torchstore_amd.api import (
     shutdown,
     stats,
 )
+from torchstore_amd.ops.quant import QuantizedTensor
 from torchstore_amd.spmd import SPMDEnv, initialize_spmd, shutdown_spmd
+from torchstore_amd.state_dict import Fp8BlockQuant
 from torchstore_amd.strategy import (
     HostStrategy,
     LocalRankStrategy,
@@ -73,6 +75,8 @@ __all__ = [
     "PlacementStrategy",
     "SingletonStrategy",
     "TransportType",
+    "Fp8BlockQuant",
+    "QuantizedTensor",
     "LocalShard",
     "Request",
     "TensorSlice",

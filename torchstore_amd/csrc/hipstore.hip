@@ -20,6 +20,9 @@
 //   * cast_copy — K3: fused dtype cast + pack (f32<->bf16/f16), one HBM
 //     read + one write, vectorized 16B/lane (reference:
 //     state_dict_utils.py:177-189 casts every floating param per sync).
+//   * quant_fp8_batch / dequant_fp8_batch — K4/K5: block-scaled FP8 (OCP
+//     e4m3, 128-element blocks, f32 scales) over N tensors in one launch
+//     each way, bit-exact against the torch recipe (csrc/quant_fp8.h).
 //   * host_register / host_unregister — pin SHM pages for DMA.
 //
 // Deliberately torch-ABI-free: tensors cross as raw device pointers +
@@ -672,25 +675,14 @@ static bool build_flat_descs(const std::vector<SliceDesc>& descs,
   return true;
 }
 
-// upload descriptors through a ring slot's pinned staging buffer + launch
-static void launch_slice_descs(std::vector<SliceDesc>& descs, uint64_t units,
-                               int device, hipStream_t stream,
-                               uint32_t tile, bool remote = false) {
-  if (units == 0 || descs.empty()) return;
-  std::vector<FlatDesc> flat;
-  uint64_t flat_units = 0;
-  uint32_t span = 0;
-  bool is_flat = false;
-  if (!remote && use_flat_kernel()) {
-    span = pick_flat_span();
-    is_flat = build_flat_descs(descs, span, flat, flat_units);
-    if (is_flat && flat_units == 0) return;  // nothing but empty copies
-  }
-  const void* payload = is_flat ? (const void*)flat.data()
-                                : (const void*)descs.data();
-  size_t bytes = is_flat ? flat.size() * sizeof(FlatDesc)
-                         : descs.size() * sizeof(SliceDesc);
-
+// Copy `bytes` of descriptors to the device through the next ring slot and
+// run `launch(d_desc)`, which enqueues on `stream` the one kernel that reads
+// them.  The slot's event is recorded behind that kernel, so the slot is
+// reused only once the kernel is done.
+template <typename Launch>
+static void stage_descs_and_launch(int device, hipStream_t stream,
+                                   const void* payload, size_t bytes,
+                                   Launch&& launch) {
   DevicePool& p = pool_for(device);
   HIP_CHECK(hipSetDevice(device));
   DescSlot* slot;
@@ -710,36 +702,60 @@ static void launch_slice_descs(std::vector<SliceDesc>& descs, uint64_t units,
   std::memcpy(slot->h_desc, payload, bytes);
   HIP_CHECK(hipMemcpyAsync(slot->d_desc, slot->h_desc, bytes,
                            hipMemcpyHostToDevice, stream));
-  const bool nt = use_nt_stores();
-  if (is_flat) {
-    // one block per unit, interleaved; memory-bound, so cap the grid
-    uint32_t grid = (uint32_t)std::min<uint64_t>(
-        flat_units, pick_grid_cap(kFlatGridDefault));
-    const char* ntl_e = getenv("HIPSTORE_FLAT_NTLOAD");
-    const bool ntl = ntl_e ? atoi(ntl_e) != 0 : true;
-    auto kern = nt ? (ntl ? copy_flat_kernel<true, true>
-                          : copy_flat_kernel<true, false>)
-                   : (ntl ? copy_flat_kernel<false, true>
-                          : copy_flat_kernel<false, false>);
-    hipLaunchKernelGGL(kern, dim3(grid), dim3(256), 0, stream,
-                       reinterpret_cast<const FlatDesc*>(slot->d_desc),
-                       (uint32_t)flat.size(), flat_units, span);
-    g_flat_launches.fetch_add(1, std::memory_order_relaxed);
-  } else {
-    // memory-bound: cap the grid and chunk units over it (guide G11);
-    // each block consumes 4 contiguous unit ranges (one per wave)
-    uint32_t grid = (uint32_t)std::min<uint64_t>((units + 3) / 4,
-                                                 pick_grid_cap(8192u));
-    auto kern = nt ? (remote ? copy_slices_kernel<true, true>
-                             : copy_slices_kernel<true, false>)
-                   : (remote ? copy_slices_kernel<false, true>
-                             : copy_slices_kernel<false, false>);
-    hipLaunchKernelGGL(kern, dim3(grid), dim3(256), 0, stream,
-                       reinterpret_cast<const SliceDesc*>(slot->d_desc),
-                       (uint32_t)descs.size(), units, tile);
-  }
+  launch(slot->d_desc);
   HIP_CHECK(hipGetLastError());
   HIP_CHECK(hipEventRecord(slot->evt, stream));
+}
+
+// upload descriptors through a ring slot's pinned staging buffer + launch
+static void launch_slice_descs(std::vector<SliceDesc>& descs, uint64_t units,
+                               int device, hipStream_t stream,
+                               uint32_t tile, bool remote = false) {
+  if (units == 0 || descs.empty()) return;
+  std::vector<FlatDesc> flat;
+  uint64_t flat_units = 0;
+  uint32_t span = 0;
+  bool is_flat = false;
+  if (!remote && use_flat_kernel()) {
+    span = pick_flat_span();
+    is_flat = build_flat_descs(descs, span, flat, flat_units);
+    if (is_flat && flat_units == 0) return;  // nothing but empty copies
+  }
+  const void* payload = is_flat ? (const void*)flat.data()
+                                : (const void*)descs.data();
+  size_t bytes = is_flat ? flat.size() * sizeof(FlatDesc)
+                         : descs.size() * sizeof(SliceDesc);
+
+  const bool nt = use_nt_stores();
+  stage_descs_and_launch(device, stream, payload, bytes, [&](void* d_desc) {
+    if (is_flat) {
+      // one block per unit, interleaved; memory-bound, so cap the grid
+      uint32_t grid = (uint32_t)std::min<uint64_t>(
+          flat_units, pick_grid_cap(kFlatGridDefault));
+      const char* ntl_e = getenv("HIPSTORE_FLAT_NTLOAD");
+      const bool ntl = ntl_e ? atoi(ntl_e) != 0 : true;
+      auto kern = nt ? (ntl ? copy_flat_kernel<true, true>
+                            : copy_flat_kernel<true, false>)
+                     : (ntl ? copy_flat_kernel<false, true>
+                            : copy_flat_kernel<false, false>);
+      hipLaunchKernelGGL(kern, dim3(grid), dim3(256), 0, stream,
+                         reinterpret_cast<const FlatDesc*>(d_desc),
+                         (uint32_t)flat.size(), flat_units, span);
+      g_flat_launches.fetch_add(1, std::memory_order_relaxed);
+    } else {
+      // memory-bound: cap the grid and chunk units over it (guide G11);
+      // each block consumes 4 contiguous unit ranges (one per wave)
+      uint32_t grid = (uint32_t)std::min<uint64_t>((units + 3) / 4,
+                                                   pick_grid_cap(8192u));
+      auto kern = nt ? (remote ? copy_slices_kernel<true, true>
+                               : copy_slices_kernel<true, false>)
+                     : (remote ? copy_slices_kernel<false, true>
+                               : copy_slices_kernel<false, false>);
+      hipLaunchKernelGGL(kern, dim3(grid), dim3(256), 0, stream,
+                         reinterpret_cast<const SliceDesc*>(d_desc),
+                         (uint32_t)descs.size(), units, tile);
+    }
+  });
 }
 
 // trivial desc for a flat byte copy (used by copy_batch's same-device path)
@@ -984,6 +1000,12 @@ static void cast_copy(uintptr_t src, int src_dtype, uintptr_t dst,
 }
 
 // ---------------------------------------------------------------------------
+// K4/K5 — block-scaled FP8 quantise / dequantise (batched)
+// ---------------------------------------------------------------------------
+
+#include "quant_fp8.h"
+
+// ---------------------------------------------------------------------------
 // host pinning
 // ---------------------------------------------------------------------------
 
@@ -1040,6 +1062,18 @@ PYBIND11_MODULE(_hipstore, m) {
   m.def("cast_copy", &cast_copy, py::arg("src"), py::arg("src_dtype"),
         py::arg("dst"), py::arg("dst_dtype"), py::arg("numel"),
         py::arg("device"), py::arg("stream"));
+  // one launch over N tensors each, async on the caller's stream; items are
+  // (wide_ptr, payload_ptr, scales_ptr, rows, cols, wide_dtype)
+  m.def("quant_fp8_batch", &quant_fp8_launch<false>, py::arg("items"),
+        py::arg("device"), py::arg("stream"),
+        py::call_guard<py::gil_scoped_release>());
+  m.def("dequant_fp8_batch", &quant_fp8_launch<true>, py::arg("items"),
+        py::arg("device"), py::arg("stream"),
+        py::call_guard<py::gil_scoped_release>());
+  m.def("quant_launches", []() {
+    return g_quant_launches.load(std::memory_order_relaxed);
+  });
+  m.attr("QUANT_BLOCK") = kQuantBlock;
   m.def("sdma_copy", &sdma_copy, py::arg("dst"), py::arg("src"),
         py::arg("nbytes"), py::arg("device"),
         py::call_guard<py::gil_scoped_release>());

@@ -4,6 +4,7 @@ The extension is built in-tree for gfx950 (``python setup.py build_ext
 --inplace``) and provides:
 
 * K1 slice-gather / K2 batched multi-slice-scatter / K3 fused cast kernels;
+* K4/K5 batched block-scaled FP8 quantise / dequantise kernels;
 * HIP IPC: export/open ``hipIpcMemHandle_t``, batched peer copies on
   dedicated streams, event completion;
 * host page pinning (``hipHostRegister``) for the SHM transport.
@@ -98,6 +99,43 @@ def cast_copy(src: torch.Tensor, out: torch.Tensor) -> None:
         src.data_ptr(), sc, out.data_ptr(), dc,
         src.numel(), src.device.index, _stream(src.device),
     )
+
+
+def _quant_items(triples):
+    items = []
+    for wide, payload, scales in triples:
+        if not (
+            wide.is_contiguous()
+            and payload.is_contiguous()
+            and scales.is_contiguous()
+        ):
+            raise ValueError("fp8 quant kernels require contiguous tensors")
+        cols = wide.shape[-1]
+        rows = wide.numel() // cols if cols else 0
+        items.append(
+            (wide.data_ptr(), payload.data_ptr(), scales.data_ptr(),
+             rows, cols, _DTYPE_CODES[wide.dtype])
+        )
+    return items
+
+
+def quant_fp8_batch(triples, device: torch.device) -> None:
+    """K4: ``[(src, payload, scales), ...]`` — block-scaled FP8 quantise of
+    N tensors in ONE launch on the caller's current stream (async)."""
+    ext().quant_fp8_batch(_quant_items(triples), device.index, _stream(device))
+
+
+def dequant_fp8_batch(triples, device: torch.device) -> None:
+    """K5: ``[(dst, payload, scales), ...]`` — the mirror image of K4; the
+    destination dtype (f32/bf16/f16) decides the output rounding."""
+    ext().dequant_fp8_batch(
+        _quant_items(triples), device.index, _stream(device)
+    )
+
+
+def quant_launches() -> int:
+    """Launches of K4 + K5 so far (tests observe the batching with it)."""
+    return ext().quant_launches()
 
 
 def _slice_desc(src: torch.Tensor, dst: torch.Tensor):

@@ -13,22 +13,91 @@ Reference semantics (torchstore ``state_dict_utils.py``):
 
 On GPU the dtype cast uses the fused cast+pack HIP kernel (K3) so the
 staging copy and the cast are one kernel pass.
+
+``transfer_quant`` ships and stores selected entries as block-scaled FP8
+(``ops/quant.py``): the payload travels under the entry's usual key, its
+scales under ``"{key}/<FP8_SCALES>/{flat_key}"``, and the commit marker —
+a :class:`QuantMapping` — records which flat keys are quantised and their
+original dtype, so readers learn it from the fetch they already make.
 """
 
 from __future__ import annotations
 
 import asyncio
+import fnmatch
 import os
-from typing import Any, Dict, List, Optional
+from dataclasses import dataclass
+from typing import Any, Dict, List, Optional, Sequence, Tuple, Union
 
 import torch
 
 from torchstore_amd.client import LocalClient
+from torchstore_amd.ops.quant import (
+    QUANT_DTYPES,
+    QuantizedTensor,
+    alloc_quantized,
+    dequantize_fp8_into,
+    quantize_fp8,
+    scales_shape,
+)
 from torchstore_amd.utils.logging import LatencyTracker, get_logger
 
 logger = get_logger("torchstore_amd.state_dict")
 
 MAPPING_KEY = "<MAPPING>"
+# scales of quantised entries live under this reserved segment, next to
+# <MAPPING>: a flat key never starts with an angle-bracket segment of ours
+SCALES_KEY = "<FP8_SCALES>"
+
+
+@dataclass(frozen=True)
+class Fp8BlockQuant:
+    """``transfer_quant`` policy: block-scaled FP8 e4m3, blocks of 128.
+
+    A state_dict entry is quantised when it is a plain ``torch.Tensor`` (no
+    subclass, so DTensor entries are left alone) of dtype f32/bf16/f16 with
+    at least one dimension and ``min_numel`` elements, whose flat key matches
+    none of the ``exclude`` fnmatch patterns.
+    """
+
+    min_numel: int = 0
+    exclude: Sequence[str] = ()
+
+    def selects(self, flat_key: str, value: Any) -> bool:
+        return (
+            type(value) is torch.Tensor
+            and value.dtype in QUANT_DTYPES
+            and value.dim() >= 1
+            and value.numel() >= self.min_numel
+            and not any(fnmatch.fnmatchcase(flat_key, p) for p in self.exclude)
+        )
+
+
+def _resolve_quant(
+    transfer_quant: Union[None, str, Fp8BlockQuant]
+) -> Optional[Fp8BlockQuant]:
+    if transfer_quant is None or isinstance(transfer_quant, Fp8BlockQuant):
+        return transfer_quant
+    if transfer_quant == "fp8_e4m3":
+        return Fp8BlockQuant()
+    raise ValueError(
+        f"unknown transfer_quant {transfer_quant!r}: expected 'fp8_e4m3' or "
+        "an Fp8BlockQuant"
+    )
+
+
+class QuantMapping(dict):
+    """The commit marker of a quantised push: the usual flat-key mapping plus
+    ``quant``, ``{flat_key: original dtype}`` of the quantised entries.  A
+    plain push keeps writing a plain dict, so readers tell the two apart
+    from the marker they fetch anyway."""
+
+    def __init__(self, mapping=(), quant: Optional[Dict[str, torch.dtype]] = None):
+        super().__init__(mapping)
+        self.quant = dict(quant or {})
+
+    def __reduce__(self):
+        return (QuantMapping, (dict(self), self.quant))
 
 # pipeline factor: big state_dicts move as N concurrent sub-batches so RPC
 # framing/parsing overlaps the volume's bulk copies
@@ -87,6 +156,71 @@ def _nbytes(flat: Dict[str, Any]) -> int:
     return total
 
 
+def _scales_beside_payloads(
+    fetches: Dict[str, Any], key: str, flat_keys
+) -> Dict[str, Any]:
+    """Order ``fetches`` so every scales entry follows its payload: ``_split``
+    cuts by entry count, and scales trailing at the end would leave all the
+    bytes in the first sub-batches."""
+    out: Dict[str, Any] = {}
+    for k in flat_keys:
+        out[f"{key}/{k}"] = fetches[f"{key}/{k}"]
+        sk = f"{key}/{SCALES_KEY}/{k}"
+        if sk in fetches:
+            out[sk] = fetches[sk]
+    return out
+
+
+def _plan_quant_dests(
+    key: str,
+    user_flat: Dict[str, Any],
+    quant: Dict[str, torch.dtype],
+    fetches: Dict[str, Any],
+) -> List[Tuple[Tuple[torch.Tensor, torch.Tensor], torch.Tensor]]:
+    """Point the fetches of quantised entries at FP8 destinations.
+
+    A ``QuantizedTensor`` leaf receives payload and scales in place.  A
+    tensor leaf gets scratch buffers on its own device; the returned
+    ``[((payload, scales), dest), ...]`` is what remains to dequantise once
+    the fetches have landed.
+    """
+    wanted = [k for k in user_flat if k in quant]
+    if not wanted:
+        return []
+    by_device: Dict[torch.device, List[str]] = {}
+    for k in wanted:
+        leaf = user_flat[k]
+        if isinstance(leaf, QuantizedTensor):
+            if tuple(leaf.scales.shape) != scales_shape(leaf.payload.shape):
+                raise ValueError(
+                    f"QuantizedTensor destination for {k!r}: scales shape "
+                    f"{tuple(leaf.scales.shape)} does not belong to a payload "
+                    f"of shape {tuple(leaf.payload.shape)}"
+                )
+            fetches[f"{key}/{k}"] = leaf.payload
+            fetches[f"{key}/{SCALES_KEY}/{k}"] = leaf.scales
+        elif (
+            type(leaf) is torch.Tensor
+            and leaf.dtype in QUANT_DTYPES
+            and leaf.dim() >= 1
+        ):
+            by_device.setdefault(leaf.device, []).append(k)
+        else:
+            raise TypeError(
+                f"entry {k!r} was pushed quantised: its destination must be "
+                "a plain f32/bf16/f16 tensor or a QuantizedTensor, got "
+                f"{type(leaf).__name__}"
+            )
+    pending = []
+    for device, ks in by_device.items():
+        bufs = alloc_quantized([user_flat[k].shape for k in ks], device)
+        for k, (payload, scales) in zip(ks, bufs):
+            fetches[f"{key}/{k}"] = payload
+            fetches[f"{key}/{SCALES_KEY}/{k}"] = scales
+            pending.append(((payload, scales), user_flat[k]))
+    return pending
+
+
 # per-(client, key) direct-sync endpoints, built lazily on first use
 _direct_sources: Dict[tuple, Any] = {}
 _direct_dests: Dict[tuple, Any] = {}
@@ -101,8 +235,15 @@ async def put_state_dict(
     rank: Optional[int] = None,
     world_size: Optional[int] = None,
     direct_rdma: bool = False,  # reference-compat alias for ``direct``
+    transfer_quant: Union[None, str, Fp8BlockQuant] = None,
 ) -> None:
     direct = direct or direct_rdma
+    quant = _resolve_quant(transfer_quant)
+    if direct and quant is not None:
+        raise ValueError(
+            "transfer_quant is not supported with direct=True: quantised "
+            "direct sync needs shard-aware scale geometry (docs/ROADMAP.md)"
+        )
     if direct:
         from torchstore_amd.weight_sync import DirectWeightSyncSource
 
@@ -118,8 +259,28 @@ async def put_state_dict(
     tracker = LatencyTracker(f"put_state_dict[{key}]")
     flat, mapping = _flatten(state_dict)
     tracker.step("flatten")
-    flat = _cast_floating(flat, transfer_dtype)
-    tracker.step("cast")
+    if quant is not None:
+        # the whole dict in one kernel launch, before the split into
+        # sub-batches; the other floating entries still take transfer_dtype
+        qkeys = [k for k, v in flat.items() if quant.selects(k, v)]
+        pairs = dict(zip(qkeys, quantize_fp8([flat[k] for k in qkeys])))
+        mapping = QuantMapping(mapping, {k: flat[k].dtype for k in qkeys})
+        rest = _cast_floating(
+            {k: v for k, v in flat.items() if k not in pairs}, transfer_dtype
+        )
+        # scales ride next to their payload, so the sub-batches of the
+        # pipeline stay balanced in bytes
+        staged: Dict[str, Any] = {}
+        for k in flat:
+            if k in pairs:
+                staged[k], staged[f"{SCALES_KEY}/{k}"] = pairs[k]
+            else:
+                staged[k] = rest[k]
+        flat = staged
+        tracker.step("quant+cast")
+    else:
+        flat = _cast_floating(flat, transfer_dtype)
+        tracker.step("cast")
     prefixed = {f"{key}/{k}": v for k, v in flat.items()}
     await asyncio.gather(
         *(client.put_batch(chunk) for chunk in _split(prefixed, _PIPELINE))
@@ -138,7 +299,14 @@ async def get_state_dict(
     strict: bool = True,
     direct: bool = False,
     direct_rdma: bool = False,  # reference-compat alias for ``direct``
+    dequantize: bool = True,
 ) -> Dict[str, Any]:
+    """``dequantize`` matters only for entries pushed with ``transfer_quant``
+    and only when no ``user_state_dict`` is given: ``False`` returns them as
+    :class:`QuantizedTensor` leaves instead of tensors of the original
+    dtype.  With a ``user_state_dict`` the destination leaf decides: a
+    tensor (f32/bf16/f16) is dequantised into, a ``QuantizedTensor`` receives
+    payload and scales as stored."""
     direct = direct or direct_rdma
     if direct:
         from torchstore_amd.weight_sync import DirectWeightSyncDest
@@ -160,6 +328,9 @@ async def get_state_dict(
             f"no state_dict was pushed under {key!r} (missing commit marker)"
         ) from exc
     tracker.step("mapping")
+    # {flat_key: original dtype} of the quantised entries; empty for a
+    # plain push, and then everything below is what it always was
+    quant: Dict[str, torch.dtype] = getattr(mapping, "quant", {})
 
     if user_state_dict is not None:
         user_flat, user_mapping = _flatten(user_state_dict)
@@ -178,6 +349,9 @@ async def get_state_dict(
                     f"stored-only entries {sorted(extra)[:5]}"
                 )
         fetches = {f"{key}/{k}": v for k, v in user_flat.items()}
+        pending = _plan_quant_dests(key, user_flat, quant, fetches)
+        if quant:
+            fetches = _scales_beside_payloads(fetches, key, user_flat)
         chunks = await asyncio.gather(
             *(
                 client.get_batch(c)
@@ -188,13 +362,25 @@ async def get_state_dict(
         for c in chunks:
             results.update(c)
         tracker.step("get_batch", _nbytes(user_flat))
-        flat = {k: results[f"{key}/{k}"] for k in user_flat}
+        flat = {
+            k: user_flat[k] if k in quant else results[f"{key}/{k}"]
+            for k in user_flat
+        }
+        if pending:
+            # one batched dequant lands in the user's tensors in place
+            dequantize_fp8_into(
+                [pair for pair, _ in pending], [dst for _, dst in pending]
+            )
+            tracker.step("dequant")
         out = _unflatten(flat, user_mapping)
         tracker.e2e(_nbytes(user_flat))
         return out
 
     flat_keys = list(mapping.keys())
     fetches = {f"{key}/{k}": None for k in flat_keys}
+    if quant:
+        fetches.update({f"{key}/{SCALES_KEY}/{k}": None for k in quant})
+        fetches = _scales_beside_payloads(fetches, key, flat_keys)
     chunks = await asyncio.gather(
         *(
             client.get_batch(c)
@@ -206,6 +392,25 @@ async def get_state_dict(
         results.update(c)
     tracker.step("get_batch")
     flat = {k: results[f"{key}/{k}"] for k in flat_keys}
+    if quant:
+        leaves = {
+            k: QuantizedTensor(
+                flat[k], results[f"{key}/{SCALES_KEY}/{k}"], dtype
+            )
+            for k, dtype in quant.items()
+        }
+        if dequantize:
+            outs = [
+                torch.empty(q.shape, dtype=q.orig_dtype, device=q.payload.device)
+                for q in leaves.values()
+            ]
+            dequantize_fp8_into(
+                [(q.payload, q.scales) for q in leaves.values()], outs
+            )
+            flat.update(zip(leaves.keys(), outs))
+            tracker.step("dequant")
+        else:
+            flat.update(leaves)
     out = _unflatten(flat, mapping)
     tracker.e2e(_nbytes(flat))
     return out
