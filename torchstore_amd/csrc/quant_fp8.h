@@ -1,8 +1,5 @@
 // Block-scaled FP8 (OCP e4m3) quantise / dequantise kernels — K4/K5.
 //
-// Included from hipstore.hip (same translation unit): uses its HIP_CHECK,
-// DType, convert<>, flat_v4u/flat_gv4u and the DescSlot ring.
-//
 // Format (per tensor, rows = the last dimension, blocks of 128 elements, the
 // last block of a row may be short):
 //   amax  = max(max|x| over the block, 2^-96)
@@ -29,31 +26,21 @@
 
 #pragma once
 
-static constexpr uint32_t kQuantBlock = 128;
-static constexpr uint32_t kQuantPasses = 2;
-static constexpr uint32_t kQuantUnitBlocks = 32 * kQuantPasses;
+#include "common.h"
+#include "desc_ring.h"
+#include "plan.h"
+#include "unit_walk.h"
+
+#include <algorithm>
+#include <atomic>
+
 static constexpr float kFp8Max = 448.0f;
 static constexpr float kAmaxFloor = 0x1p-96f;
-
-struct QuantDesc {
-  uintptr_t wide;         // f32/bf16/f16 tensor: quant source, dequant dest
-  uintptr_t payload;      // e4m3 bytes, same element order as `wide`
-  uintptr_t scales;       // f32 [rows, nblk]
-  uint64_t rows;
-  uint64_t units_prefix;  // exclusive prefix sum of units
-  uint32_t cols;
-  uint32_t nblk;          // blocks per row = ceil(cols / 128)
-  uint32_t nblocks;       // rows * nblk
-  uint32_t dtype;         // DType of `wide`
-  uint32_t fast;          // 1 = 16B-vector path
-  uint32_t pad_;
-};
-static_assert(sizeof(QuantDesc) == 64, "QuantDesc is meant to be 64 bytes");
 
 // 16 elements of T as raw 16B vectors (sizeof(T) of them)
 template <typename T>
 struct QuantRaw {
-  flat_v4u q[sizeof(T)];
+  v4u q[sizeof(T)];
 };
 
 __device__ __forceinline__ float group8_max(float a) {
@@ -120,9 +107,9 @@ __device__ __forceinline__ void quant_unit(const QuantDesc& d,
         eoff[p] += gl * 16u;
       }
 #pragma unroll
-      for (uint32_t k = 0; k < sizeof(T); ++k) raw[p].q[k] = flat_v4u{0, 0, 0, 0};
+      for (uint32_t k = 0; k < sizeof(T); ++k) raw[p].q[k] = v4u{0, 0, 0, 0};
       if (live[p]) {
-        const flat_gv4u* s = reinterpret_cast<const flat_gv4u*>(
+        const gv4u* s = reinterpret_cast<const gv4u*>(
             d.wide + eoff[p] * sizeof(T));
 #pragma unroll
         for (uint32_t k = 0; k < sizeof(T); ++k) raw[p].q[k] = s[k];
@@ -143,7 +130,7 @@ __device__ __forceinline__ void quant_unit(const QuantDesc& d,
       // dead lanes hold zeros, so they add nothing to the block's amax
       amax = fmaxf(group8_max(amax), kAmaxFloor);
       const float inv = kFp8Max / amax;
-      flat_v4u out;
+      v4u out;
 #pragma unroll
       for (uint32_t w = 0; w < 4; ++w) {
         int packed = 0;
@@ -156,7 +143,7 @@ __device__ __forceinline__ void quant_unit(const QuantDesc& d,
         out[w] = (uint32_t)packed;
       }
       if (live[p]) {
-        *reinterpret_cast<flat_gv4u*>(d.payload + eoff[p]) = out;
+        *reinterpret_cast<gv4u*>(d.payload + eoff[p]) = out;
       }
       if (gl == 0 && gb < d.nblocks) scales[gb] = amax / kFp8Max;
     }
@@ -204,7 +191,7 @@ __device__ __forceinline__ void dequant_unit(const QuantDesc& d,
   const uint32_t gb0 = local_unit * kQuantUnitBlocks + group;
   const float* scales = reinterpret_cast<const float*>(d.scales);
   if (d.fast) {
-    flat_v4u raw[kQuantPasses];
+    v4u raw[kQuantPasses];
     float scale[kQuantPasses];
     uint64_t eoff[kQuantPasses];
     bool live[kQuantPasses];
@@ -219,10 +206,10 @@ __device__ __forceinline__ void dequant_unit(const QuantDesc& d,
         live[p] = col0 + gl * 16u < d.cols;
         eoff[p] += gl * 16u;
       }
-      raw[p] = flat_v4u{0, 0, 0, 0};
+      raw[p] = v4u{0, 0, 0, 0};
       scale[p] = 0.0f;
       if (live[p]) {
-        raw[p] = *reinterpret_cast<const flat_gv4u*>(d.payload + eoff[p]);
+        raw[p] = *reinterpret_cast<const gv4u*>(d.payload + eoff[p]);
         // the 8 lanes of a group read one address: a single broadcast fetch
         scale[p] = scales[gb];
       }
@@ -242,8 +229,8 @@ __device__ __forceinline__ void dequant_unit(const QuantDesc& d,
       }
       QuantRaw<T> out;
       __builtin_memcpy(&out, e, sizeof(e));
-      flat_gv4u* dst =
-          reinterpret_cast<flat_gv4u*>(d.wide + eoff[p] * sizeof(T));
+      gv4u* dst =
+          reinterpret_cast<gv4u*>(d.wide + eoff[p] * sizeof(T));
 #pragma unroll
       for (uint32_t k = 0; k < sizeof(T); ++k) dst[k] = out.q[k];
     }
@@ -271,19 +258,10 @@ template <bool DEQUANT>
 __global__ void __launch_bounds__(256)
 quant_fp8_kernel(const QuantDesc* __restrict__ descs, uint32_t ndescs,
                  uint64_t total_units) {
-  uint32_t lo = 0;  // units only grow, so the search never moves back
+  UnitWalk w;
   QuantDesc d = {};
-  uint64_t next_prefix = 0;  // forces the lookup on the first unit
   for (uint64_t unit = blockIdx.x; unit < total_units; unit += gridDim.x) {
-    if (unit >= next_prefix) {
-      uint32_t hi = ndescs - 1;
-      while (lo < hi) {
-        uint32_t mid = (lo + hi + 1) >> 1;
-        if (descs[mid].units_prefix <= unit) lo = mid; else hi = mid - 1;
-      }
-      d = descs[lo];
-      next_prefix = (lo + 1 < ndescs) ? descs[lo + 1].units_prefix : ~0ull;
-    }
+    if (unit >= w.next_prefix) walk_seek(w, d, descs, ndescs, unit);
     const uint32_t local = (uint32_t)(unit - d.units_prefix);
     // d is uniform over the workgroup, so every wave takes one branch whole
     // and the 8-lane shuffles inside always see all 64 lanes active
@@ -307,64 +285,19 @@ quant_fp8_kernel(const QuantDesc* __restrict__ descs, uint32_t ndescs,
 // launches of either kernel (tests check the batching through this)
 static std::atomic<uint64_t> g_quant_launches{0};
 
-// grid cap (workgroups); HIPSTORE_QUANT_GRID overrides.  The sweep on 1 GiB of
-// bf16 (profiles/quant_sync.log) kept gaining up to 65536, about one unit per
-// workgroup, as the flat copy kernel did: 5.6 TB/s quant and 5.4 TB/s dequant
-// against 4.9 / 4.8 at the cast kernel's 1024
-static uint32_t pick_quant_grid_cap() {
-  const char* e = getenv("HIPSTORE_QUANT_GRID");
-  uint32_t forced = e ? (uint32_t)atoi(e) : 0u;
-  return forced >= 64 ? forced : 65536u;
-}
-
-// python passes per tensor:
-//   (wide_ptr, payload_ptr, scales_ptr, rows, cols, wide_dtype)
-using PyQuantItem =
-    std::tuple<uintptr_t, uintptr_t, uintptr_t, uint64_t, uint64_t, int>;
-
+// One launch of either kernel, async on `stream`.  Grid cap (workgroups):
+// the sweep on 1 GiB of bf16 (profiles/quant_sync.log) kept gaining up to
+// 65536, about one unit per workgroup, as the flat copy kernel did: 5.6 TB/s
+// quant and 5.4 TB/s dequant against 4.9 / 4.8 at the cast kernel's 1024
 template <bool DEQUANT>
-static void quant_fp8_launch(const std::vector<PyQuantItem>& items, int device,
-                             uintptr_t stream_handle) {
-  std::vector<QuantDesc> descs;
-  descs.reserve(items.size());
-  uint64_t units = 0;
-  for (const auto& it : items) {
-    QuantDesc d{};
-    d.wide = std::get<0>(it);
-    d.payload = std::get<1>(it);
-    d.scales = std::get<2>(it);
-    d.rows = std::get<3>(it);
-    const uint64_t cols = std::get<4>(it);
-    const int dtype = std::get<5>(it);
-    if (dtype < 0 || dtype > 2) throw std::runtime_error("unsupported dtype");
-    if (d.rows == 0 || cols == 0) continue;
-    const uint64_t nblk = (cols + kQuantBlock - 1) / kQuantBlock;
-    const uint64_t nblocks = d.rows * nblk;
-    if (cols > UINT32_MAX || nblocks > (1ull << 31))
-      throw std::runtime_error("tensor too large for one quant descriptor");
-    if (d.scales & 3u) throw std::runtime_error("scales must be 4B aligned");
-    const uint32_t es = dtype == 0 ? 4u : 2u;
-    if (d.wide % es) throw std::runtime_error("misaligned tensor");
-    d.cols = (uint32_t)cols;
-    d.nblk = (uint32_t)nblk;
-    d.nblocks = (uint32_t)nblocks;
-    d.dtype = (uint32_t)dtype;
-    d.fast = (((d.wide | d.payload) & 15u) == 0 && (cols & 15u) == 0) ? 1u : 0u;
-    d.units_prefix = units;
-    units += (nblocks + kQuantUnitBlocks - 1) / kQuantUnitBlocks;
-    descs.push_back(d);
-  }
-  if (descs.empty()) return;
-  hipStream_t stream = reinterpret_cast<hipStream_t>(stream_handle);
-  const uint32_t grid =
-      (uint32_t)std::min<uint64_t>(units, pick_quant_grid_cap());
-  const uint32_t n = (uint32_t)descs.size();
-  stage_descs_and_launch(
-      device, stream, descs.data(), descs.size() * sizeof(QuantDesc),
-      [&](void* d_desc) {
-        hipLaunchKernelGGL(quant_fp8_kernel<DEQUANT>, dim3(grid), dim3(256), 0,
-                           stream, reinterpret_cast<const QuantDesc*>(d_desc),
-                           n, units);
-      });
+static void launch_quant_fp8(const Plan<QuantDesc>& p, int device,
+                             hipStream_t stream) {
+  if (p.descs.empty()) return;
+  const uint32_t grid = (uint32_t)std::min<uint64_t>(
+      p.units, env_u32("HIPSTORE_QUANT_GRID", 64, UINT32_MAX, 65536));
+  stage_descs_and_launch(device, stream, p.descs, [&](const QuantDesc* d) {
+    hipLaunchKernelGGL(quant_fp8_kernel<DEQUANT>, dim3(grid), dim3(256), 0,
+                       stream, d, (uint32_t)p.descs.size(), p.units);
+  });
   g_quant_launches.fetch_add(1, std::memory_order_relaxed);
 }

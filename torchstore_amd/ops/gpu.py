@@ -138,28 +138,50 @@ def quant_launches() -> int:
     return ext().quant_launches()
 
 
-def _slice_desc(src: torch.Tensor, dst: torch.Tensor):
-    """Build a copy_slices descriptor; None when the pair doesn't qualify."""
-    if src.shape != dst.shape or src.dtype != dst.dtype:
-        return None
+# a contiguous source below this many bytes is ONE flat descriptor; the
+# native row length is 32-bit, so anything larger takes the row form
+_FLAT_DESC_MAX_BYTES = 1 << 32
+
+_CONTIGUOUS = "contiguous"
+
+
+def _copy_desc(src: torch.Tensor, dst_ptr: int, dst_strides):
+    """copy_slices descriptor: strided ``src`` view → ``dst_ptr``.
+
+    ``dst_strides`` are the destination's byte strides (one per dim of
+    ``src``) or ``"contiguous"``.  Returns ``()`` for an empty view and None
+    when the kernel cannot express the copy (non-unit inner stride).
+    """
     if src.numel() == 0:
         return ()
     es = src.element_size()
     if src.dim() == 0:
-        return (src.data_ptr(), dst.data_ptr(), es, [], [], [])
+        return (src.data_ptr(), dst_ptr, es, [], [], [])
+    nbytes = src.numel() * es
     if (
         src.is_contiguous()
-        and dst.is_contiguous()
-        and src.numel() * es < (1 << 32)
+        and dst_strides == _CONTIGUOUS
+        and nbytes < _FLAT_DESC_MAX_BYTES
     ):
-        return (src.data_ptr(), dst.data_ptr(), src.numel() * es, [], [], [])
-    if src.stride(-1) != 1 or dst.stride(-1) != 1:
+        # flat descriptor: full tiles, no per-row offset math
+        return (src.data_ptr(), dst_ptr, nbytes, [], [], [])
+    if src.stride(-1) != 1:
         return None
     row_bytes = src.shape[-1] * es
     outer = list(src.shape[:-1])
     sst = [s * es for s in src.stride()[:-1]]
-    dstst = [s * es for s in dst.stride()[:-1]]
-    return (src.data_ptr(), dst.data_ptr(), row_bytes, outer, sst, dstst)
+    if dst_strides == _CONTIGUOUS:
+        dstst = []
+        acc = row_bytes
+        for d in reversed(outer):
+            dstst.append(acc)
+            acc *= d
+        dstst.reverse()
+    elif dst_strides[-1] != es:
+        return None
+    else:
+        dstst = list(dst_strides[:-1])
+    return (src.data_ptr(), dst_ptr, row_bytes, outer, sst, dstst)
 
 
 # large 2-D copies route to SDMA pitched engines (hipMemcpy2D moves a
@@ -178,6 +200,67 @@ def _pitched_params(t: torch.Tensor):
     return None
 
 
+def _slice_desc(src: torch.Tensor, dst: torch.Tensor):
+    """Descriptor for a tensor pair; None when the pair doesn't qualify."""
+    if src.shape != dst.shape or src.dtype != dst.dtype:
+        return None
+    if dst.is_contiguous():
+        return _copy_desc(src, dst.data_ptr(), _CONTIGUOUS)
+    es = dst.element_size()
+    return _copy_desc(src, dst.data_ptr(), [s * es for s in dst.stride()])
+
+
+def _desc_view_to_ptr(src: torch.Tensor, dst_ptr: int):
+    """Descriptor: strided src view → contiguous bytes at a raw pointer."""
+    return _copy_desc(src, dst_ptr, _CONTIGUOUS)
+
+
+def _pair_pitches(src: torch.Tensor, dst: torch.Tensor):
+    sp = _pitched_params(src)
+    dp = _pitched_params(dst)
+    if sp and dp and sp[1:] == dp[1:]:
+        return (dst.data_ptr(), dp[0], sp[0], sp[1], sp[2])
+    return None
+
+
+def _view_pitches(src: torch.Tensor, dst_ptr: int):
+    sp = None if src.is_contiguous() else _pitched_params(src)
+    return (dst_ptr, sp[1], sp[0], sp[1], sp[2]) if sp else None
+
+
+def _dispatch(items, device, blocking, pitches_of, desc_of, on_reject):
+    """One kernel launch + the SDMA 2-D copies for ``[(src, dst), ...]``.
+
+    ``pitches_of(src, dst)`` — ``(dst_ptr, dst_pitch, src_pitch, width,
+    height)`` in bytes, or None — is asked for items of _SDMA_2D_MIN_BYTES
+    and more and sends them to the SDMA pitched engines; ``desc_of(src,
+    dst)`` describes the rest for the kernel.  ``on_reject(item)`` runs, in
+    order, for each item neither can express.
+    """
+    descs = []
+    sdma2d = []
+    for item in items:
+        src, dst = item
+        if src.numel() * src.element_size() >= _SDMA_2D_MIN_BYTES:
+            p = pitches_of(src, dst)
+            if p is not None:
+                dst_ptr, dpitch, spitch, width, height = p
+                sdma2d.append(
+                    (dst_ptr, device.index, dpitch,
+                     src.data_ptr(), device.index, spitch, width, height)
+                )
+                continue
+        d = desc_of(src, dst)
+        if d is None:
+            on_reject(item)
+        elif d != ():
+            descs.append(d)
+    if descs:
+        ext().copy_slices(descs, device.index, _stream(device), blocking)
+    if sdma2d:
+        ext().copy_batch_2d(sdma2d)  # synchronizes internally
+
+
 def copy_pairs(
     pairs, device: torch.device, blocking: bool = True
 ) -> None:
@@ -187,90 +270,27 @@ def copy_pairs(
     pitched engines; the rest batch into one kernel launch; pairs neither
     can express fall back to ``copy_``.
     """
-    descs = []
-    sdma2d = []
-    for src, dst in pairs:
-        nbytes = src.numel() * src.element_size()
-        if nbytes >= _SDMA_2D_MIN_BYTES:
-            sp = _pitched_params(src)
-            dp = _pitched_params(dst)
-            if sp and dp and sp[1] == dp[1] and sp[2] == dp[2]:
-                sdma2d.append(
-                    (dst.data_ptr(), device.index, dp[0],
-                     src.data_ptr(), device.index, sp[0], sp[1], sp[2])
-                )
-                continue
-        d = _slice_desc(src, dst)
-        if d is None:
-            dst.copy_(src)
-        elif d != ():
-            descs.append(d)
-    if descs:
-        ext().copy_slices(descs, device.index, _stream(device), blocking)
-    if sdma2d:
-        ext().copy_batch_2d(sdma2d)  # synchronizes internally
-
-
-def _desc_view_to_ptr(src: torch.Tensor, dst_ptr: int):
-    """Descriptor: strided src view → contiguous bytes at a raw pointer.
-
-    Fuses K1 (gather) with the transfer itself: the kernel reads the
-    stored view and writes straight into the (same-device) peer-mapped
-    destination — no packed intermediate, half the HBM traffic.
-    """
-    if src.numel() == 0:
-        return ()
-    es = src.element_size()
-    nbytes = src.numel() * es
-    if src.dim() == 0:
-        return (src.data_ptr(), dst_ptr, es, [], [], [])
-    if src.is_contiguous():
-        # flat descriptor: full 16 KiB tiles, no per-row offset math
-        return (src.data_ptr(), dst_ptr, nbytes, [], [], [])
-    if src.stride(-1) != 1:
-        return None
-    row_bytes = src.shape[-1] * es
-    outer = list(src.shape[:-1])
-    sst = [s * es for s in src.stride()[:-1]]
-    # contiguous destination strides for src.shape
-    dstst = []
-    acc = row_bytes
-    for d in reversed(outer):
-        dstst.append(acc)
-        acc *= d
-    dstst = list(reversed(dstst))
-    return (src.data_ptr(), dst_ptr, row_bytes, outer, sst, dstst)
+    _dispatch(
+        pairs, device, blocking, _pair_pitches, _slice_desc,
+        lambda pair: pair[1].copy_(pair[0]),
+    )
 
 
 def copy_views_to_ptrs(items, device: torch.device, blocking: bool = True):
     """Batched fused gather+write: ``[(src_view, dst_ptr), ...]``.
 
+    Fuses K1 (gather) with the transfer itself: the kernel reads the stored
+    view and writes straight into contiguous bytes at the (same-device)
+    peer-mapped destination — no packed intermediate, half the HBM traffic.
     Large strided 2-D sources use SDMA pitched copies; the rest batch into
     one kernel launch.  Returns the items neither could express (caller
     falls back to pack+copy for those).
     """
-    descs = []
-    sdma2d = []
     rejects = []
-    for src, dst_ptr in items:
-        nbytes = src.numel() * src.element_size()
-        if nbytes >= _SDMA_2D_MIN_BYTES and not src.is_contiguous():
-            sp = _pitched_params(src)
-            if sp:
-                sdma2d.append(
-                    (dst_ptr, device.index, sp[1],
-                     src.data_ptr(), device.index, sp[0], sp[1], sp[2])
-                )
-                continue
-        d = _desc_view_to_ptr(src, dst_ptr)
-        if d is None:
-            rejects.append((src, dst_ptr))
-        elif d != ():
-            descs.append(d)
-    if descs:
-        ext().copy_slices(descs, device.index, _stream(device), blocking)
-    if sdma2d:
-        ext().copy_batch_2d(sdma2d)  # synchronizes internally
+    _dispatch(
+        items, device, blocking, _view_pitches, _desc_view_to_ptr,
+        rejects.append,
+    )
     return rejects
 
 
