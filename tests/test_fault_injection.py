@@ -8,7 +8,7 @@ not poison the pair cache (publish-on-success).
 
 The fakes replace only the native byte movers (export/resolve/copy) with
 in-process equivalents (ctypes.memmove between CPU tensors), so the FULL
-client↔volume protocol — double-buffered windows, commit ordering, abort —
+client↔volume protocol — pipelined windows, commit ordering, abort —
 runs exactly as on hardware.
 """
 
@@ -341,3 +341,117 @@ def test_pull_abort_releases_stash(pushpull_env, monkeypatch):
             buffer._batched_pull([(0, Request(key="k"), dest)], {0: None})
         )
     assert not cache.pull_stash
+
+
+# -- shared rules of the HIP-IPC transport ---------------------------------
+@pytest.mark.parametrize("sizes,cap,slots,buffers", [
+    ([100, 256, 257, 1], 1024,
+     [(0, 0), (0, 256), (0, 512), (1, 0)], [(1024, 1024), (256, 256)]),
+    ([300, 300, 300], 512,
+     [(0, 0), (1, 0), (2, 0)], [(512, 512)] * 3),
+    ([1, 1], 1 << 20, [(0, 0), (0, 256)], [(512, 512)]),
+    ([], 1024, [], []),
+    ([0, 5, 0], 1024, [(0, 0), (0, 0), (0, 256)], [(256, 256)]),
+    ([1024, 1], 1024, [(0, 0), (1, 0)], [(1024, 1024), (256, 256)]),
+])
+def test_plan_slots_pins(sizes, cap, slots, buffers):
+    """Values computed from the rule the put packs and get bounces shared
+    before the planner existed (new buffer when the slot does not fit, sized
+    min(cap, max(remaining, slot)))."""
+    assert hip_ipc._plan_slots(sizes, cap) == (slots, buffers)
+
+
+def test_plan_slots_properties():
+    import random
+
+    rng = random.Random(20240611)
+    for _ in range(400):
+        cap = rng.choice([256, 512, 1024, 4096, 1 << 16])
+        sizes = [
+            rng.choice([0, 1, 255, 256, 257, rng.randint(0, cap)])
+            for _ in range(rng.randint(0, 24))
+        ]
+        sizes = [min(n, cap) for n in sizes]
+        slots, buffers = hip_ipc._plan_slots(sizes, cap)
+        assert len(slots) == len(sizes)  # exactly one slot per input
+        spans = {}
+        for n, (b, off) in zip(sizes, slots):
+            assert 0 <= b < len(buffers) and off % 256 == 0
+            assert off + n <= buffers[b][1], "slot pokes past used bytes"
+            if n:
+                spans.setdefault(b, []).append((off, off + n))
+        for b, (alloc, used) in enumerate(buffers):
+            assert used <= alloc <= cap
+            taken = sorted(spans.get(b, []))
+            for (_s0, e0), (s1, _e1) in zip(taken, taken[1:]):
+                assert e0 <= s1, "slots of one buffer overlap"
+
+
+def test_reuse_or_alloc():
+    cpu = torch.device("cpu")
+    prior = torch.zeros(4, 6)
+    assert isinstance(prior.shape, torch.Size)
+    assert hip_ipc._reuse_or_alloc(prior, (4, 6), torch.float32, cpu) is prior
+    assert hip_ipc._reuse_or_alloc(prior, prior.shape, torch.float32, cpu) is prior
+    for got in (
+        hip_ipc._reuse_or_alloc(prior, (6, 4), torch.float32, cpu),
+        hip_ipc._reuse_or_alloc(prior, (4, 6), torch.float64, cpu),
+        hip_ipc._reuse_or_alloc(prior.t(), (6, 4), torch.float32, cpu),
+        hip_ipc._reuse_or_alloc(None, (4, 6), torch.float32, cpu),
+    ):
+        assert got is not prior and got.data_ptr() != prior.data_ptr()
+        assert got.is_contiguous() and got.device == cpu
+    assert not prior.t().is_contiguous()
+
+
+def test_handshake_unknown_phase(chunked_env):
+    buffer, volume, _ctx = chunked_env
+    with pytest.raises(ValueError, match="unknown handshake phase"):
+        buffer.recv_handshake(None, "chunk_put_rollback", volume)
+
+
+def test_handshake_table_covers_every_sent_phase(pushpull_env, monkeypatch):
+    """Drive every client path (windowed put/get, push, pull, and the abort
+    of each releasing kind) and check that each phase string the client sent
+    is a key of the dispatch table — and that none of the table is unused."""
+    buffer, volume, volume_ctx = pushpull_env
+    sent = set()
+    real_call = volume.call_one
+
+    async def recording(buf, args, phase):
+        sent.add(phase)
+        assert phase in HipIpcTransportBuffer._PHASES, phase
+        return await real_call(buf, args, phase)
+
+    volume.call_one = recording
+    stored = torch.arange(2500, dtype=torch.uint8)
+    volume.store = _FakeStore(stored)
+    dest = torch.zeros_like(stored)
+
+    async def drive():
+        await buffer._chunked_get_windows(Request(key="k"), dest)
+        await buffer._batched_pull([(0, Request(key="k"), dest)], {0: None})
+        volume.store = None  # the fake store serves gets only
+        await buffer._chunked_put_windows(torch.arange(1200, dtype=torch.uint8))
+        await buffer._push_put(
+            [(0, torch.ones(64, dtype=torch.uint8))],
+            [Request(key="a")], [("pending", None)],
+        )
+        # aborts: the windowed and push paths release only on failure
+        volume.fail_at = ("chunk_put_commit", volume._counts["chunk_put_commit"])
+        with pytest.raises(RuntimeError, match="injected"):
+            await buffer._chunked_put_windows(torch.zeros(8, dtype=torch.uint8))
+
+        def boom(copies):
+            raise RuntimeError("injected copy failure")
+
+        monkeypatch.setattr(hip_ipc, "_run_copies", boom)
+        with pytest.raises(RuntimeError, match="injected"):
+            await buffer._push_put(
+                [(0, torch.ones(8, dtype=torch.uint8))],
+                [Request(key="a")], [("pending", None)],
+            )
+
+    asyncio.run(drive())
+    assert sent == set(HipIpcTransportBuffer._PHASES)
+    assert len(sent) == 9

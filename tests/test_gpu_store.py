@@ -504,6 +504,113 @@ async def test_packed_put_coalescing(monkeypatch):
     await _with_store(body, transport=TransportType.HIP_IPC)
 
 
+def _force_unexportable_staging(monkeypatch):
+    """Fake a cross-device volume and make the CLIENT's pack and bounce
+    buffers (the only 1-D uint8 tensors it exports; user tensors here are
+    float) unexportable, as if they had landed in >=2 GiB blocks."""
+    from torchstore_amd.transport import hip_ipc
+
+    monkeypatch.setattr(
+        hip_ipc.HipIpcTransportBuffer, "_volume_device_index", lambda self: 7
+    )
+    real_export = hip_ipc.try_export
+    refused = []
+
+    def export(t, generation=None):
+        if t.dtype == torch.uint8 and t.dim() == 1:
+            refused.append(t.numel())
+            return None
+        return real_export(t, generation)
+
+    monkeypatch.setattr(hip_ipc, "try_export", export)
+    return hip_ipc.HipIpcTransportBuffer, refused
+
+
+@requires_gpu
+async def test_packed_put_degrades_when_pack_unexportable(monkeypatch):
+    """A pack buffer that cannot be exported degrades every packed entry to
+    individual staging ("ipc"), byte-exact."""
+    buffer_cls, refused = _force_unexportable_staging(monkeypatch)
+    kinds = []
+    real_stage = buffer_cls.client_stage_put
+
+    async def stage(self, requests):
+        await real_stage(self, requests)
+        kinds.extend(
+            kind for (kind, _v), r in zip(self.payload, requests)
+            if not r.is_object
+        )
+
+    monkeypatch.setattr(buffer_cls, "client_stage_put", stage)
+
+    async def body():
+        items = {f"d{i}": torch.randn(64, 65, device="cuda") for i in range(6)}
+        items["tiny"] = torch.randn(7, device="cuda", dtype=torch.bfloat16)
+        items["zero_d"] = torch.tensor(3.5, device="cuda")
+        await ts.put_batch(items)
+        assert kinds and all(k == "ipc" for k in kinds), kinds
+        assert len(kinds) == len(items)
+        assert refused, "the pack buffer export was never attempted"
+        for k, v in items.items():
+            out = await ts.get(k)
+            assert out.dtype == v.dtype and out.shape == v.shape, k
+            assert torch.equal(out, v), k
+
+    await _with_store(body, transport=TransportType.HIP_IPC)
+
+
+@requires_gpu
+async def test_bounce_get_degrades_when_bounce_unexportable(monkeypatch):
+    """A bounce buffer that cannot be exported degrades every bounce entry
+    to per-request staging; the strided dest goes through a dense scratch."""
+    from torchstore_amd.types import LocalShard, TensorSlice
+
+    buffer_cls, refused = _force_unexportable_staging(monkeypatch)
+    staged = []  # (kinds, strided request indices, scratch indices)
+    real_stage = buffer_cls.client_stage_get
+
+    async def stage(self, requests):
+        await real_stage(self, requests)
+        staged.append((
+            [kind for kind, _v in self.payload],
+            {i for i, r in enumerate(requests)
+             if not r.tensor_val.is_contiguous()},
+            set(self._scratch),
+        ))
+
+    async def body():
+        items = {f"g{i}": torch.randn(64, 65, device="cuda") for i in range(4)}
+        wide = torch.randn(128, 128, device="cuda")
+        await ts.put_batch({**items, "wide": wide})
+        refused.clear()
+        monkeypatch.setattr(buffer_cls, "client_stage_get", stage)
+        dests = {k: torch.zeros_like(v) for k, v in items.items()}
+        backing = torch.zeros(128, 96, device="cuda")
+        region = backing[:, :64]  # strided (128, 64) destination
+        assert not region.is_contiguous()
+        dests["wide"] = LocalShard(
+            tensor=region,
+            slice=TensorSlice(
+                offsets=(0, 32), local_shape=(128, 64),
+                global_shape=(128, 128), coordinates=(), mesh_shape=(),
+            ),
+        )
+        out = await ts.get_batch(dests)
+        torch.cuda.synchronize()
+        for k, v in items.items():
+            assert torch.equal(out[k], v), k
+        assert torch.equal(region, wide[:, 32:96])
+        assert torch.count_nonzero(backing[:, 64:]) == 0
+        assert refused, "the bounce buffer export was never attempted"
+        assert len(staged) == 1
+        kinds, strided, scratch = staged[0]
+        assert len(kinds) == 5 and "bounce" not in kinds, kinds
+        assert all(k == "ipc" for k in kinds), kinds
+        assert len(strided) == 1 and strided <= scratch, (strided, scratch)
+
+    await _with_store(body, transport=TransportType.HIP_IPC)
+
+
 @requires_gpu
 async def test_fake8_reshard_topology(monkeypatch):
     """The 8-rank fsdp→tp reshard flow dry-run on ONE GPU: 8 volumes (all

@@ -39,11 +39,19 @@ blocks:
 
 CPU tensors and objects in a batch ride inline in the RPC frame (an IPC
 batch can be mixed — e.g. a state_dict with scalar stats).
+
+**Layout.**  Module-level helpers hold the rules several paths share
+(``_reuse_or_alloc``, ``_plan_slots``, ``_windows``); the buffer class opens
+with the table of payload kinds, then the handshake phases (one
+``_on_<phase>`` method each), then put (classify → pack per device → sync →
+export, degrade → push, windowed) and get (classify → bounce layout →
+pulls), each followed by its volume side.
 """
 
 from __future__ import annotations
 
 import asyncio
+import contextlib
 import os
 import uuid
 from dataclasses import dataclass
@@ -67,6 +75,8 @@ IPC_BLOCK_LIMIT = 1 << 31
 # (profiles/ipc_sweep: fewer per-window RPCs, same overlap)
 CHUNK_BYTES = int(os.environ.get("TORCHSTORE_AMD_IPC_CHUNK_MB", "1024")) << 20
 
+Copy = Tuple[int, int, int, int, int]  # dst_ptr, dst_dev, src_ptr, src_dev, nbytes
+
 
 @dataclass(frozen=True)
 class IpcDescriptor:
@@ -78,25 +88,103 @@ class IpcDescriptor:
     device_index: int      # exporter's GPU
 
 
-def _ext():
-    from torchstore_amd.ops import gpu
+_OPS = None
 
-    return gpu.ext()
+
+def _ops():
+    """``(ops.gpu, ops.slicing.byte_view)``, imported on first use; ``gpu`` is
+    the module, so its functions are still looked up at call time."""
+    global _OPS
+    if _OPS is None:
+        from torchstore_amd.ops import gpu
+        from torchstore_amd.ops.slicing import byte_view
+
+        _OPS = (gpu, byte_view)
+    return _OPS
+
+
+def _ext():
+    return _ops()[0].ext()
+
+
+def _nbytes(t: torch.Tensor) -> int:
+    return t.numel() * t.element_size()
+
+
+def _reuse_or_alloc(prior, shape, dtype, device) -> torch.Tensor:
+    """``prior`` (the tensor already stored under the key) when a re-put can
+    be written INTO it, else a fresh tensor — a fresh multi-GB hipMalloc per
+    re-put cost ~30 ms and doubled peak memory."""
+    if (
+        prior is not None
+        and tuple(prior.shape) == tuple(shape)
+        and prior.dtype == dtype
+        and prior.is_contiguous()
+        and prior.device == device
+    ):
+        return prior
+    return torch.empty(shape, dtype=dtype, device=device)
+
+
+def _stored_prior(volume, meta) -> Optional[torch.Tensor]:
+    store = getattr(volume, "store", None)
+    if meta is None or store is None:
+        return None
+    return store.find_existing(meta)
+
+
+def _aligned(nbytes: int) -> int:
+    return (nbytes + 255) & ~255
+
+
+def _plan_slots(nbytes_list: Sequence[int], cap: int):
+    """Lay 256-byte-aligned slots into byte buffers of at most ``cap``.
+
+    Returns ``(slots, buffers)`` with ``slots[k] = (buffer_idx, offset)`` and
+    ``buffers[b] = (alloc_bytes, used_bytes)``.  A new buffer opens when a
+    slot does not fit and is sized for all that is still to come, capped so
+    it stays exportable; a zero-byte entry takes the current offset without
+    advancing it.  Pure arithmetic — allocation and export are the caller's.
+    """
+    sizes = [_aligned(n) for n in nbytes_list]
+    remaining = sum(sizes)
+    slots: List[Tuple[int, int]] = []
+    buffers: List[Tuple[int, int]] = []
+    size = off = 0
+    for a in sizes:
+        if not buffers or off + a > size:
+            if buffers:
+                buffers[-1] = (size, off)
+            size = min(cap, max(remaining, a))
+            buffers.append((size, 0))
+            off = 0
+        slots.append((len(buffers) - 1, off))
+        off += a
+        remaining -= a
+    if buffers:
+        buffers[-1] = (size, off)
+    return slots, buffers
+
+
+def _windows(nbytes: int) -> List[Tuple[int, int]]:
+    """``(offset, length)`` of every CHUNK_BYTES window of the windowed path."""
+    return [
+        (off, min(CHUNK_BYTES, nbytes - off))
+        for off in range(0, nbytes, CHUNK_BYTES)
+    ]
 
 
 class BlockTooLargeError(RuntimeError):
     pass
 
 
-def export_tensor(
-    t: torch.Tensor, generation: Optional[int] = None
-) -> IpcDescriptor:
+def export_tensor(t: torch.Tensor, generation: Optional[int] = None) -> IpcDescriptor:
     """Export; raises :class:`BlockTooLargeError` for ≥2 GiB blocks."""
     desc = try_export(t, generation)
     if desc is None:
         raise BlockTooLargeError(
             f"tensor lives in a >=2GiB allocator block "
-            f"({t.numel() * t.element_size()} bytes); peers cannot map it — "
+            f"({_nbytes(t)} bytes); peers cannot map it — "
             "use the chunked transport path"
         )
     return desc
@@ -109,10 +197,8 @@ def try_export(
     (``ops.gpu.alloc_generation``); batch call sites compute it once per
     device per batch, cold paths let it default."""
     assert t.is_contiguous() and t.device.type == "cuda"
-    from torchstore_amd.ops import gpu
-
     if generation is None:
-        generation = gpu.alloc_generation(t.device.index)
+        generation = _ops()[0].alloc_generation(t.device.index)
     handle, offset, block_size = _ext().ipc_export(
         t.data_ptr(), t.device.index, generation
     )
@@ -121,7 +207,7 @@ def try_export(
     return IpcDescriptor(
         handle=bytes(handle),
         offset=offset,
-        nbytes=t.numel() * t.element_size(),
+        nbytes=_nbytes(t),
         dtype=t.dtype,
         shape=tuple(t.shape),
         device_index=t.device.index,
@@ -155,13 +241,18 @@ class IpcOpenCache(TransportCache):
 
 
 class ChunkStagingCache(TransportCache):
-    """Volume-side pool of <2 GiB staging chunks for the windowed path.
+    """Volume-side per-token state of the ≥2 GiB strategies.
 
-    An operation acquires THREE chunks: the client's chunk-reuse
-    distance then tolerates the volume's ASYNC commit copies (a commit
-    reply only guarantees the PREVIOUS window's copy), so client xGMI
-    copies, volume copies and commit RPCs all overlap.  Also owns the
-    direct push/pull per-op state (pending payloads / pinned exports).
+    * windowed path: ``free`` is the pool of <2 GiB staging chunks,
+      ``by_token`` an operation's chunks and payload, ``op_streams`` its
+      async commit stream.  An operation acquires THREE chunks: the
+      client's chunk-reuse distance then tolerates the volume's ASYNC
+      commit copies (a commit reply only guarantees the PREVIOUS window's
+      copy), so client xGMI copies, volume copies and commit RPCs overlap;
+    * direct push: ``push_pending`` holds the payload tensors the CLIENT
+      writes into until ``volume_receive`` takes them;
+    * direct pull: ``pull_stash`` pins the exported values alive while the
+      client reads them.
     """
 
     def __init__(self):
@@ -172,27 +263,16 @@ class ChunkStagingCache(TransportCache):
         ] = {}
         # async put-commit state: token -> (torch stream, last event)
         self.op_streams: Dict[str, Tuple[Any, Any]] = {}
-        # direct push/pull state (no staging hop):
-        #   push: token -> payload tensors the CLIENT writes into directly
-        #   pull: token -> value tensors pinned alive while the client reads
         self.push_pending: Dict[str, List[Optional[torch.Tensor]]] = {}
         self.pull_stash: Dict[str, List[Optional[torch.Tensor]]] = {}
 
-    def acquire(
-        self,
-        token: str,
-        payload: torch.Tensor,
-        device: torch.device,
-        nchunks: int = 3,
-    ) -> List[IpcDescriptor]:
+    def acquire(self, token, payload, device, nchunks=3) -> List[IpcDescriptor]:
         chunks: List[Tuple[torch.Tensor, IpcDescriptor]] = []
         for _ in range(nchunks):
             if self.free:
                 chunks.append(self.free.pop())
             else:
-                staging = torch.empty(
-                    CHUNK_BYTES, dtype=torch.uint8, device=device
-                )
+                staging = torch.empty(CHUNK_BYTES, dtype=torch.uint8, device=device)
                 chunks.append((staging, export_tensor(staging)))
         self.by_token[token] = (chunks, payload)
         return [desc for _s, desc in chunks]
@@ -203,9 +283,7 @@ class ChunkStagingCache(TransportCache):
     def staging(self, token: str, idx: int = 0) -> torch.Tensor:
         return self.by_token[token][0][idx][0]
 
-    def commit_async(
-        self, token: str, device: torch.device, copy_fn
-    ) -> None:
+    def commit_async(self, token: str, device: torch.device, copy_fn) -> None:
         """Run a window's staging→payload copy on the op's own stream.
 
         Returning from the commit RPC then only guarantees the PREVIOUS
@@ -249,6 +327,28 @@ class ChunkStagingCache(TransportCache):
         self.free.extend(chunks)
         return payload
 
+    def hold_pushed(self, token: str, payloads) -> None:
+        self.push_pending[token] = payloads
+
+    def take_pushed(self, token: str, j: int) -> torch.Tensor:
+        """Payload j of a push, for the store; the token goes with its last."""
+        pending = self.push_pending.get(token)
+        if pending is None or pending[j] is None:
+            raise RuntimeError("pushed put token unknown")
+        payload, pending[j] = pending[j], None
+        if all(p is None for p in pending):
+            self.push_pending.pop(token, None)
+        return payload
+
+    def drop_pushed(self, token: str) -> None:
+        self.push_pending.pop(token, None)
+
+    def pin_pulled(self, token: str, values) -> None:
+        self.pull_stash[token] = values
+
+    def drop_pulled(self, token: str) -> None:
+        self.pull_stash.pop(token, None)
+
     def drop_key(self, key: str) -> None:
         return None
 
@@ -261,26 +361,52 @@ class ChunkStagingCache(TransportCache):
         self.pull_stash.clear()
 
 
-def _run_copies(copies: List[Tuple[int, int, int, int, int]]) -> None:
+def _run_copies(copies: List[Copy]) -> None:
     """(dst_ptr, dst_dev, src_ptr, src_dev, nbytes) batch on the stream pool."""
     if copies:
         _ext().copy_batch(copies)
 
 
 class HipIpcTransportBuffer(TransportBuffer):
+    # ``payload`` is aligned with the requests, one (kind, value) each.
+    #
+    # put: written by client_stage_put, consumed by volume_receive
+    #   "inline"   value          object or CPU tensor, rides the frame
+    #   "ipc"      IpcDescriptor  client tensor, the volume pulls it
+    #   "packed"   (pack_idx, off, shape, dtype)  slot of client pack buffer
+    #              pack_descs[pack_idx]; the volume pulls the buffer, scatters
+    #   "pushed"   (token, j)     from _push_put: the client has filled volume
+    #              payload j of the token; the volume takes it
+    #   "chunked"  token          from _chunked_put_windows: the payload is
+    #              complete under the token; the volume takes it, frees chunks
+    #   "pending"  None           client-only placeholder until export decides
+    # get: written by client_stage_get, consumed by volume_send
+    #   "fetch_obj", "fetch_inline"  object / CPU dest, answered "inline"
+    #   "ipc"      IpcDescriptor  dest or its dense _scratch, the volume writes it
+    #   "bounce"   (b_idx, off, nbytes)  slot of client bounce buffer
+    #              bounce_descs[b_idx]; client_complete_get reads it back
+    #   "pending_pull" None       client-only placeholder until _batched_pull
+    #   "pulled"   None           from _batched_pull: the client already copied
+    #              out of the volume's pinned export
+    #   "chunked"  token          from _chunked_get_windows: the windows are
+    #              delivered; the volume only frees the chunks
+    # reply: written by volume_send, consumed by client_complete_get
+    #   "inline"   value          copied into the dest, or returned as it is
+    #   "done"     None           the bytes are in the dest (or its scratch)
+    #   "bounced"  None           the bytes are in the request's bounce slot
     transport_type = TransportType.HIP_IPC
     requires_handshake = False
 
+    PACK_THRESHOLD = 32 << 20   # cross-device tensors below this coalesce
+    PACK_BUF_CAP = 512 << 20    # per pack buffer (stays exportable)
+    BOUNCE_BUF_CAP = 1 << 30    # per bounce buffer, well under the 2GiB limit
+
     def __init__(self):
         super().__init__()
-        # aligned with requests:
-        #   ("ipc", IpcDescriptor) | ("inline", value) | ("chunked", token)
-        #   ("packed", (pack_idx, offset, shape, dtype)) — put coalescing
-        #   get-side markers: ("fetch_obj"|"fetch_inline", None)
         self.payload: Optional[List[Tuple[str, Any]]] = None
         self.bounce_descs: List[IpcDescriptor] = []
         # put-side coalescing: (desc, used_bytes) per client pack buffer
-        self.pack_descs: List[Tuple[IpcDescriptor, int]] = []
+        self.pack_descs: List[Tuple[Optional[IpcDescriptor], int]] = []
         self._packs: List[torch.Tensor] = []
         self._hold: List[torch.Tensor] = []       # keep exports alive
         self._scratch: Dict[int, torch.Tensor] = {}  # req idx -> dense scratch
@@ -297,13 +423,32 @@ class HipIpcTransportBuffer(TransportBuffer):
         state["_packs"] = []
         return state
 
+    @contextlib.asynccontextmanager
+    async def _releasing(self, token: str, phase: str, always: bool = False):
+        """Abort phase: when the body fails (or ``always``), send ``phase`` so
+        the volume frees what it holds under ``token`` — a failed transfer
+        must not leak volume resources.  The release's own failure is
+        swallowed."""
+        failed = True
+        try:
+            yield
+            failed = False
+        finally:
+            if failed or always:
+                try:
+                    await self._volume_ref.volume.handshake.call_one(
+                        self, token, phase
+                    )
+                except Exception:  # noqa: BLE001
+                    pass
+
     # -- chunked windows (client side) -----------------------------------
     async def _chunked_put_windows(
         self, t: torch.Tensor, request: Optional[Request] = None
     ) -> str:
         """Stream a big tensor into volume staging, window by window.
 
-        Double-buffered over two staging chunks: while window N's commit
+        Pipelined over the op's three staging chunks: while window N's commit
         RPC is in flight, window N+1's xGMI copy runs concurrently (in an
         executor thread — the C++ copy drops the GIL)."""
         volume = self._volume_ref.volume
@@ -313,18 +458,11 @@ class HipIpcTransportBuffer(TransportBuffer):
         staging_descs = await volume.handshake.call_one(
             self, (token, meta, tuple(t.shape), t.dtype), "chunk_put_init"
         )
-        try:
-            ptrs = [
-                cache.resolve(d, t.device.index) for d in staging_descs
-            ]
-            nbytes = t.numel() * t.element_size()
+        async with self._releasing(token, "chunk_release"):
+            ptrs = [cache.resolve(d, t.device.index) for d in staging_descs]
             base = t.data_ptr()
-            windows = [
-                (off, min(CHUNK_BYTES, nbytes - off))
-                for off in range(0, nbytes, CHUNK_BYTES)
-            ]
             commit_task = None
-            for i, (off, win) in enumerate(windows):
+            for i, (off, win) in enumerate(_windows(_nbytes(t))):
                 c = i % len(ptrs)
                 await asyncio.to_thread(
                     _run_copies,
@@ -340,40 +478,29 @@ class HipIpcTransportBuffer(TransportBuffer):
                 )
             if commit_task is not None:
                 await commit_task
-        except BaseException:
-            # abort: return the staging chunks to the pool (uniflow's abort
-            # phase — a failed transfer must not leak volume resources)
-            try:
-                await volume.handshake.call_one(self, token, "chunk_release")
-            except Exception:  # noqa: BLE001
-                pass
-            raise
         return token
 
-    async def _chunked_get_windows(
-        self, request: Request, dest: torch.Tensor
-    ) -> str:
-        """Windowed fetch, double-buffered: window N's xGMI copy out of one
-        staging chunk overlaps window N+1's fill RPC into the other."""
+    async def _chunked_get_windows(self, request: Request, dest: torch.Tensor) -> str:
+        """Windowed fetch, pipelined over the op's three staging chunks:
+        window N's xGMI copy out of its chunk overlaps window N+1's fill RPC
+        into the next."""
         volume = self._volume_ref.volume
         cache: IpcOpenCache = self._client_ctx.cache(IpcOpenCache)
         token = uuid.uuid4().hex
         staging_descs = await volume.handshake.call_one(
             self, (token, request.meta_only()), "chunk_get_init"
         )
-        try:
-            ptrs = [
-                cache.resolve(d, dest.device.index) for d in staging_descs
-            ]
-            nbytes = dest.numel() * dest.element_size()
+        async with self._releasing(token, "chunk_release"):
+            ptrs = [cache.resolve(d, dest.device.index) for d in staging_descs]
             base = dest.data_ptr()
-            windows = [
-                (off, min(CHUNK_BYTES, nbytes - off))
-                for off in range(0, nbytes, CHUNK_BYTES)
-            ]
+
+            def drain(c: int, off: int, win: int) -> List[Copy]:
+                return [(base + off, dest.device.index,
+                         ptrs[c], staging_descs[c].device_index, win)]
+
             fill_task = None
             prev: Optional[Tuple[int, int, int]] = None  # (chunk, off, win)
-            for i, (off, win) in enumerate(windows):
+            for i, (off, win) in enumerate(_windows(_nbytes(dest))):
                 c = i % len(ptrs)
                 if fill_task is not None:
                     await fill_task
@@ -383,174 +510,166 @@ class HipIpcTransportBuffer(TransportBuffer):
                     )
                 )
                 if prev is not None:
-                    pc, poff, pwin = prev
                     # copy the PREVIOUS (already filled) window while the
                     # current fill RPC runs — different chunks, no overlap
-                    await asyncio.to_thread(
-                        _run_copies,
-                        [(base + poff, dest.device.index,
-                          ptrs[pc], staging_descs[pc].device_index, pwin)],
-                    )
+                    await asyncio.to_thread(_run_copies, drain(*prev))
                 prev = (c, off, win)
             if fill_task is not None:
                 await fill_task
             if prev is not None:
-                pc, poff, pwin = prev
-                await asyncio.to_thread(
-                    _run_copies,
-                    [(base + poff, dest.device.index,
-                      ptrs[pc], staging_descs[pc].device_index, pwin)],
-                )
-        except BaseException:
-            try:
-                await volume.handshake.call_one(self, token, "chunk_release")
-            except Exception:  # noqa: BLE001
-                pass
-            raise
+                await asyncio.to_thread(_run_copies, drain(*prev))
         return token
 
-    # -- volume handshake dispatcher --------------------------------------
+    # -- volume handshake phases -------------------------------------------
     def recv_handshake(self, args, phase: str, volume):
+        handler = self._PHASES.get(phase)
+        if handler is None:
+            raise ValueError(f"unknown handshake phase {phase!r}")
         cache: ChunkStagingCache = self._volume_ctx.cache(ChunkStagingCache)
-        device = volume.device
-        if phase == "chunk_put_init":
-            token, meta, shape, dtype = args
-            payload = None
-            store = getattr(volume, "store", None)
-            if meta is not None and store is not None:
-                # re-put of an existing key: write INTO the stored tensor
-                # (the non-chunked path's `prior` reuse) — a fresh multi-GB
-                # hipMalloc per re-put cost ~30 ms and doubled peak memory
-                prior = store.find_existing(meta)
-                if (
-                    prior is not None
-                    and tuple(prior.shape) == tuple(shape)
-                    and prior.dtype == dtype
-                    and prior.is_contiguous()
-                    and prior.device == device
-                ):
-                    payload = prior
-            if payload is None:
-                payload = torch.empty(shape, dtype=dtype, device=device)
-            return cache.acquire(token, payload, device)
-        if phase == "chunk_put_commit":
-            token, chunk_idx, dst_off, length = args
-            staging = cache.staging(token, chunk_idx)
-            payload = cache.payload(token)
-            from torchstore_amd.ops.slicing import byte_view
+        return handler(self, cache, volume, args)
 
-            dstv = byte_view(payload)[dst_off : dst_off + length]
-            srcv = staging[:length]
+    def _on_chunk_put_init(self, cache, volume, args):
+        token, meta, shape, dtype = args
+        payload = _reuse_or_alloc(
+            _stored_prior(volume, meta), shape, dtype, volume.device
+        )
+        return cache.acquire(token, payload, volume.device)
 
-            def do_copy(stream):
-                dstv.copy_(srcv, non_blocking=stream is not None)
+    def _on_chunk_put_commit(self, cache, volume, args):
+        token, chunk_idx, dst_off, length = args
+        byte_view = _ops()[1]
+        dstv = byte_view(cache.payload(token))[dst_off : dst_off + length]
+        srcv = cache.staging(token, chunk_idx)[:length]
 
-            cache.commit_async(token, device, do_copy)
-            return "ok"
-        if phase == "chunk_get_init":
-            token, request = args
-            from torchstore_amd.ops import gpu as gpu_ops
+        def do_copy(stream):
+            dstv.copy_(srcv, non_blocking=stream is not None)
 
-            value = volume.store.fetch(request)
-            packed = gpu_ops.pack_region(value)
-            torch.cuda.current_stream(device).synchronize()
-            return cache.acquire(token, packed, device)
-        if phase == "chunk_get_fill":
-            token, chunk_idx, src_off, length = args
-            staging = cache.staging(token, chunk_idx)
-            payload = cache.payload(token)
-            _run_copies(
-                [(staging.data_ptr(), device.index,
-                  payload.data_ptr() + src_off, device.index, length)]
+        cache.commit_async(token, volume.device, do_copy)
+        return "ok"
+
+    def _on_chunk_get_init(self, cache, volume, args):
+        token, request = args
+        packed = _ops()[0].pack_region(volume.store.fetch(request))
+        torch.cuda.current_stream(volume.device).synchronize()
+        return cache.acquire(token, packed, volume.device)
+
+    def _on_chunk_get_fill(self, cache, volume, args):
+        token, chunk_idx, src_off, length = args
+        dev = volume.device.index
+        _run_copies(
+            [(cache.staging(token, chunk_idx).data_ptr(), dev,
+              cache.payload(token).data_ptr() + src_off, dev, length)]
+        )
+        return "ok"
+
+    def _on_chunk_release(self, cache, volume, token):
+        cache.release(token)
+        return "ok"
+
+    def _on_push_alloc(self, cache, volume, args):
+        # direct put of client tensors living in unexportable (>=2 GiB)
+        # blocks: the VOLUME exports the (<2 GiB) payload tensors and the
+        # client writes into them one-sided — no staging hop, no per-window
+        # RPCs (the windowed path remains the fallback for payloads that
+        # are themselves >=2 GiB)
+        token, items = args
+        payloads: List[Optional[torch.Tensor]] = []
+        descs: List[Optional[IpcDescriptor]] = []
+        for meta, shape, dtype in items:
+            payload = _reuse_or_alloc(
+                _stored_prior(volume, meta), shape, dtype, volume.device
             )
-            return "ok"
-        if phase == "chunk_release":
-            cache.release(args)
-            return "ok"
-        if phase == "push_alloc":
-            # direct put of client tensors living in unexportable (>=2 GiB)
-            # blocks: the VOLUME exports the (<2 GiB) payload tensors and
-            # the client writes into them one-sided — no staging hop, no
-            # per-window RPCs (the windowed path remains the fallback for
-            # payloads that are themselves >=2 GiB)
-            token, items = args
-            store = getattr(volume, "store", None)
-            payloads: List[Optional[torch.Tensor]] = []
-            descs: List[Optional[IpcDescriptor]] = []
-            for meta, shape, dtype in items:
-                payload = None
-                if meta is not None and store is not None:
-                    prior = store.find_existing(meta)
-                    if (
-                        prior is not None
-                        and tuple(prior.shape) == tuple(shape)
-                        and prior.dtype == dtype
-                        and prior.is_contiguous()
-                        and prior.device == device
-                    ):
-                        payload = prior
-                if payload is None:
-                    payload = torch.empty(shape, dtype=dtype, device=device)
-                desc = try_export(payload)
-                if desc is None:
-                    payloads.append(None)  # unexportable payload: fallback
-                    descs.append(None)
-                else:
-                    payloads.append(payload)
-                    descs.append(desc)
-            cache.push_pending[token] = payloads
-            return descs
-        if phase == "push_release":
-            cache.push_pending.pop(args, None)
-            return "ok"
-        if phase == "pull_init":
-            # direct get into client destinations living in unexportable
-            # blocks: the volume exports the stored values (packing strided
-            # ones) and PINS them under the token while the client reads
-            token, metas = args
-            from torchstore_amd.ops import gpu as gpu_ops
+            desc = try_export(payload)
+            # an unexportable payload is not held: the client falls back
+            payloads.append(payload if desc is not None else None)
+            descs.append(desc)
+        cache.hold_pushed(token, payloads)
+        return descs
 
-            stash: List[Optional[torch.Tensor]] = []
-            descs = []
-            launched = False
-            for meta in metas:
-                value = volume.store.fetch(meta)
-                if (
-                    isinstance(value, torch.Tensor)
-                    and value.device.type == "cpu"
-                    and device.type == "cuda"
-                ):
-                    # tier-spilled value: stage through HBM so the client
-                    # pulls at device rate instead of host-memory rate
-                    value = value.to(device)
-                if not isinstance(value, torch.Tensor) or value.device != device:
-                    stash.append(None)
-                    descs.append(None)
-                    continue
-                if value.is_contiguous():
-                    vc = value
-                else:
-                    vc = gpu_ops.pack_region(value)
-                    launched = True
-                desc = try_export(vc)
-                stash.append(vc if desc is not None else None)
-                descs.append(desc)
-            if launched:
-                torch.cuda.current_stream(device).synchronize()
-            cache.pull_stash[token] = stash
-            return descs
-        if phase == "pull_release":
-            cache.pull_stash.pop(args, None)
-            return "ok"
-        raise ValueError(f"unknown handshake phase {phase!r}")
+    def _on_push_release(self, cache, volume, token):
+        cache.drop_pushed(token)
+        return "ok"
+
+    def _on_pull_init(self, cache, volume, args):
+        # direct get into client destinations living in unexportable
+        # blocks: the volume exports the stored values (packing strided
+        # ones) and PINS them under the token while the client reads
+        token, metas = args
+        device = volume.device
+        stash: List[Optional[torch.Tensor]] = []
+        descs: List[Optional[IpcDescriptor]] = []
+        launched = False
+        for meta in metas:
+            value = volume.store.fetch(meta)
+            if (
+                isinstance(value, torch.Tensor)
+                and value.device.type == "cpu"
+                and device.type == "cuda"
+            ):
+                # tier-spilled value: stage through HBM so the client
+                # pulls at device rate instead of host-memory rate
+                value = value.to(device)
+            if not isinstance(value, torch.Tensor) or value.device != device:
+                stash.append(None)
+                descs.append(None)
+                continue
+            if value.is_contiguous():
+                vc = value
+            else:
+                vc = _ops()[0].pack_region(value)
+                launched = True
+            desc = try_export(vc)
+            stash.append(vc if desc is not None else None)
+            descs.append(desc)
+        if launched:
+            torch.cuda.current_stream(device).synchronize()
+        cache.pin_pulled(token, stash)
+        return descs
+
+    def _on_pull_release(self, cache, volume, token):
+        cache.drop_pulled(token)
+        return "ok"
+
+    _PHASES = {
+        "chunk_put_init": _on_chunk_put_init,
+        "chunk_put_commit": _on_chunk_put_commit,
+        "chunk_get_init": _on_chunk_get_init,
+        "chunk_get_fill": _on_chunk_get_fill,
+        "chunk_release": _on_chunk_release,
+        "push_alloc": _on_push_alloc,
+        "push_release": _on_push_release,
+        "pull_init": _on_pull_init,
+        "pull_release": _on_pull_release,
+    }
 
     # ------------------------------------------------------------- put --
-    PACK_THRESHOLD = 32 << 20   # cross-device tensors below this coalesce
-    PACK_BUF_CAP = 512 << 20    # per pack buffer (stays exportable)
-
     async def client_stage_put(self, requests: Sequence[Request]) -> None:
-        from torchstore_amd.ops import gpu as gpu_ops
+        payload, staged, pack_items, devices = self._classify_put(requests)
+        self.pack_descs = []
+        self._packs = []
+        pack_meta: List[Tuple[int, int, int]] = []  # (payload idx, pack idx, off)
+        by_dev: Dict[int, List[Tuple[int, torch.Tensor]]] = {}
+        for i, t in pack_items:
+            by_dev.setdefault(t.device.index, []).append((i, t))
+        for dev, items in by_dev.items():
+            self._pack_device(dev, items, payload, pack_meta)
 
+        # every producing kernel AND every pack copy must be visible before
+        # the volume's one-sided pulls read the staging memory from another
+        # process — so the sync happens once per device AFTER the whole
+        # staging loop, not at the first tensor seen
+        gens = {di: _ops()[0].alloc_generation(di) for di in devices}
+        for di in devices:
+            torch.cuda.current_stream(torch.device("cuda", di)).synchronize()
+
+        self._export_packs(requests, gens, pack_meta, staged)
+        await self._export_staged(requests, staged, gens, payload)
+        self.payload = payload
+
+    def _classify_put(self, requests: Sequence[Request]):
+        """Inline entries are final; ``staged`` (payload idx, contiguous
+        tensor) export one by one; ``pack_items`` (payload idx, tensor)
+        coalesce; ``devices`` are the GPUs to synchronise."""
         payload: List[Tuple[str, Any]] = []
         staged: List[Tuple[int, torch.Tensor]] = []
         pack_items: List[Tuple[int, torch.Tensor]] = []
@@ -564,109 +683,77 @@ class HipIpcTransportBuffer(TransportBuffer):
             if t.device.type != "cuda":
                 payload.append(("inline", t))
                 continue
-            nbytes = t.numel() * t.element_size()
             cross = vol_dev >= 0 and vol_dev != t.device.index
-            if cross and 0 < nbytes < self.PACK_THRESHOLD:
+            devices.add(t.device.index)
+            payload.append(("pending", None))
+            if cross and 0 < _nbytes(t) < self.PACK_THRESHOLD:
                 # put-side coalescing (the twin of the get-side bounce):
                 # small cross-device tensors pack into ONE staging buffer —
                 # one K1 pack launch here, one xGMI copy + one K2 scatter
                 # on the volume, instead of an SDMA enqueue per tensor
-                payload.append(("pending", None))
                 pack_items.append((len(payload) - 1, t))
-                devices.add(t.device.index)
-                continue
-            tc = t.contiguous()
-            self._hold.append(tc)
-            devices.add(tc.device.index)
-            payload.append(("pending", None))
-            staged.append((len(payload) - 1, tc))
+            else:
+                tc = t.contiguous()
+                self._hold.append(tc)
+                staged.append((len(payload) - 1, tc))
+        return payload, staged, pack_items, devices
 
-        self.pack_descs = []
-        self._packs: List[torch.Tensor] = []
-        pack_meta: List[Tuple[int, int, int]] = []  # (payload idx, pack idx, off)
-        if pack_items:
-            by_dev: Dict[int, List[Tuple[int, torch.Tensor]]] = {}
-            for i, t in pack_items:
-                by_dev.setdefault(t.device.index, []).append((i, t))
-            for dev, items in by_dev.items():
-                device = torch.device("cuda", dev)
-                sizes = [
-                    (t.numel() * t.element_size() + 255) & ~255
-                    for _i, t in items
-                ]
-                buf = None
-                off = 0
-                copies = []  # (src_view, dst_ptr) for one batched launch
-                for k, (i, t) in enumerate(items):
-                    aligned = sizes[k]
-                    if buf is None or off + aligned > buf.numel():
-                        if buf is not None:
-                            self.pack_descs[-1] = (self.pack_descs[-1][0], off)
-                        remaining = sum(sizes[k:])
-                        size = min(self.PACK_BUF_CAP, max(remaining, aligned))
-                        buf = torch.empty(size, dtype=torch.uint8, device=device)
-                        self._packs.append(buf)
-                        self._hold.append(buf)
-                        self.pack_descs.append((None, 0))  # desc filled below
-                        off = 0
-                    copies.append((t, buf.data_ptr() + off))
-                    pack_meta.append((i, len(self._packs) - 1, off))
-                    payload[i] = (
-                        "packed",
-                        (len(self._packs) - 1, off, tuple(t.shape), t.dtype),
-                    )
-                    off += aligned
-                if buf is not None:
-                    self.pack_descs[-1] = (self.pack_descs[-1][0], off)
-                rejects = gpu_ops.copy_views_to_ptrs(
-                    copies, device, blocking=False
-                )
-                if rejects:
-                    from torchstore_amd.ops.slicing import byte_view
+    def _pack_device(self, dev: int, items, payload, pack_meta) -> None:
+        """Allocate one device's pack buffers and fill them with one batched
+        launch; their export waits for the sync (``_export_packs``)."""
+        device = torch.device("cuda", dev)
+        slots, buffers = _plan_slots(
+            [_nbytes(t) for _i, t in items], self.PACK_BUF_CAP
+        )
+        first = len(self._packs)
+        for size, used in buffers:
+            buf = torch.empty(size, dtype=torch.uint8, device=device)
+            self._packs.append(buf)
+            self._hold.append(buf)
+            self.pack_descs.append((None, used))
+        copies = []  # (src_view, dst_ptr) for one batched launch
+        for (i, t), (b, off) in zip(items, slots):
+            pk = first + b
+            copies.append((t, self._packs[pk].data_ptr() + off))
+            pack_meta.append((i, pk, off))
+            payload[i] = ("packed", (pk, off, tuple(t.shape), t.dtype))
+        rejects = _ops()[0].copy_views_to_ptrs(copies, device, blocking=False)
+        if rejects:
+            # kernel-inexpressible layouts pack via torch copy.  Slot lookup
+            # by DESTINATION pointer: the same tensor object may be packed
+            # under several keys (distinct slots), so identity on the source
+            # would be ambiguous
+            byte_view = _ops()[1]
+            slot_by_ptr = {
+                self._packs[pk].data_ptr() + poff: (pk, poff)
+                for _pi, pk, poff in pack_meta
+            }
+            for t, ptr in rejects:
+                tc = t.contiguous()
+                pk, poff = slot_by_ptr[ptr]
+                self._packs[pk][poff : poff + _nbytes(tc)].copy_(byte_view(tc))
 
-                    # slot lookup by DESTINATION pointer: the same tensor
-                    # object may be packed under several keys (distinct
-                    # slots), so identity on the source would be ambiguous
-                    slot_by_ptr = {
-                        self._packs[pk].data_ptr() + poff: (pk, poff)
-                        for _pi, pk, poff in pack_meta
-                    }
-                    for t, ptr in rejects:
-                        # kernel-inexpressible layout: pack via torch copy
-                        tc = t.contiguous()
-                        pk, poff = slot_by_ptr[ptr]
-                        nb = tc.numel() * tc.element_size()
-                        self._packs[pk][poff : poff + nb].copy_(byte_view(tc))
-
-        # every producing kernel AND every pack copy must be visible before
-        # the volume's one-sided pulls read the staging memory from another
-        # process — so the sync happens once per device AFTER the whole
-        # staging loop, not at the first tensor seen
-        gens = {di: gpu_ops.alloc_generation(di) for di in devices}
-        for di in devices:
-            torch.cuda.current_stream(torch.device("cuda", di)).synchronize()
-
-        resolved_packs: List[Tuple[Optional[IpcDescriptor], int]] = []
-        for buf, (_d, used) in zip(self._packs, self.pack_descs):
-            desc = try_export(buf, gens[buf.device.index])
-            resolved_packs.append((desc, used))
-        self.pack_descs = resolved_packs
+    def _export_packs(self, requests, gens, pack_meta, staged) -> None:
+        self.pack_descs = [
+            (try_export(buf, gens[buf.device.index]), used)
+            for buf, (_d, used) in zip(self._packs, self.pack_descs)
+        ]
         for pi, pk, _off in pack_meta:
             if self.pack_descs[pk][0] is None:
                 # pack buffer landed in an unexportable (>=2 GiB) block:
                 # degrade this entry to individual staging
-                t = requests[pi].tensor_val
-                tc = t.contiguous()
+                tc = requests[pi].tensor_val.contiguous()
                 self._hold.append(tc)
                 torch.cuda.current_stream(tc.device).synchronize()
                 staged.append((pi, tc))
 
+    async def _export_staged(self, requests, staged, gens, payload) -> None:
         push_items: List[Tuple[int, torch.Tensor]] = []
         for i, tc in staged:
             desc = try_export(tc, gens.get(tc.device.index))
             if desc is not None:
                 payload[i] = ("ipc", desc)
-            elif tc.numel() * tc.element_size() < IPC_BLOCK_LIMIT:
+            elif _nbytes(tc) < IPC_BLOCK_LIMIT:
                 # the tensor itself fits an exportable block but LIVES in
                 # an unexportable (>=2 GiB) one (e.g. a view of a huge
                 # source): PUSH — the volume exports its payload and the
@@ -677,14 +764,8 @@ class HipIpcTransportBuffer(TransportBuffer):
                 payload[i] = ("chunked", token)
         if push_items:
             await self._push_put(push_items, requests, payload)
-        self.payload = payload
 
-    async def _push_put(
-        self,
-        push_items: List[Tuple[int, torch.Tensor]],
-        requests: Sequence[Request],
-        payload: List[Tuple[str, Any]],
-    ) -> None:
+    async def _push_put(self, push_items, requests, payload) -> None:
         volume = self._volume_ref.volume
         cache: IpcOpenCache = self._client_ctx.cache(IpcOpenCache)
         token = uuid.uuid4().hex
@@ -692,10 +773,8 @@ class HipIpcTransportBuffer(TransportBuffer):
             (requests[i].meta_only(), tuple(tc.shape), tc.dtype)
             for i, tc in push_items
         ]
-        descs = await volume.handshake.call_one(
-            self, (token, items), "push_alloc"
-        )
-        try:
+        descs = await volume.handshake.call_one(self, (token, items), "push_alloc")
+        async with self._releasing(token, "push_release"):
             copies = []
             chunk_fallback: List[int] = []
             for j, ((i, tc), desc) in enumerate(zip(push_items, descs)):
@@ -705,7 +784,7 @@ class HipIpcTransportBuffer(TransportBuffer):
                 dst_ptr = cache.resolve(desc, tc.device.index)
                 copies.append(
                     (dst_ptr, desc.device_index, tc.data_ptr(),
-                     tc.device.index, tc.numel() * tc.element_size())
+                     tc.device.index, _nbytes(tc))
                 )
                 payload[i] = ("pushed", (token, j))
             if copies:
@@ -714,108 +793,69 @@ class HipIpcTransportBuffer(TransportBuffer):
                 i, tc = push_items[j]
                 tok = await self._chunked_put_windows(tc, requests[i])
                 payload[i] = ("chunked", tok)
-        except BaseException:
-            try:
-                await volume.handshake.call_one(self, token, "push_release")
-            except Exception:  # noqa: BLE001
-                pass
-            raise
 
     async def volume_receive(self, requests, existing, device):
         cache: IpcOpenCache = self._volume_ctx.cache(IpcOpenCache)
         chunks: ChunkStagingCache = self._volume_ctx.cache(ChunkStagingCache)
         out: List[Any] = [None] * len(self.payload)
-        copies: List[Tuple[int, int, int, int, int]] = []
+        copies: List[Copy] = []
         # coalesced puts: (out idx, pack idx, off, shape, dtype, prior)
         pack_entries: List[Tuple[int, int, int, Tuple, Any, Any]] = []
-        for i, ((kind, value), prior) in enumerate(
-            zip(self.payload, existing)
-        ):
+        for i, ((kind, value), prior) in enumerate(zip(self.payload, existing)):
             if kind == "inline":
                 if isinstance(value, torch.Tensor):
-                    out[i] = value.to(device)
-                else:
-                    out[i] = value
-                continue
-            if kind == "chunked":
-                payload = chunks.release(value)
-                if payload is None:
+                    value = value.to(device)
+                out[i] = value
+            elif kind == "chunked":
+                out[i] = chunks.release(value)
+                if out[i] is None:
                     raise RuntimeError("chunked put token unknown")
-                out[i] = payload
-                continue
-            if kind == "pushed":
-                token, j = value
-                pending = chunks.push_pending.get(token)
-                if pending is None or pending[j] is None:
-                    raise RuntimeError("pushed put token unknown")
-                out[i] = pending[j]
-                pending[j] = None
-                if all(p is None for p in pending):
-                    chunks.push_pending.pop(token, None)
-                continue
-            if kind == "packed":
-                pk, off, shape, dtype = value
-                pack_entries.append((i, pk, off, shape, dtype, prior))
-                continue
-            desc: IpcDescriptor = value
-            src_ptr = cache.resolve(desc, device.index)
-            if (
-                prior is not None
-                and prior.shape == desc.shape
-                and prior.dtype == desc.dtype
-                and prior.is_contiguous()
-                and prior.device == device
-            ):
-                dst = prior
-            else:
-                dst = torch.empty(desc.shape, dtype=desc.dtype, device=device)
-            copies.append(
-                (dst.data_ptr(), device.index, src_ptr, desc.device_index,
-                 desc.nbytes)
-            )
-            out[i] = dst
-        pack_locals: Dict[int, torch.Tensor] = {}
-        if pack_entries:
-            # ONE xGMI copy per pack buffer's used span, then one batched
-            # K2 scatter splitting it into stored tensors
-            for pk in {e[1] for e in pack_entries}:
-                desc, used = self.pack_descs[pk]
-                local = torch.empty(used, dtype=torch.uint8, device=device)
+            elif kind == "pushed":
+                out[i] = chunks.take_pushed(*value)
+            elif kind == "packed":
+                pack_entries.append((i, *value, prior))
+            else:  # "ipc"
+                desc: IpcDescriptor = value
                 src_ptr = cache.resolve(desc, device.index)
+                dst = _reuse_or_alloc(prior, desc.shape, desc.dtype, device)
                 copies.append(
-                    (local.data_ptr(), device.index, src_ptr,
-                     desc.device_index, used)
+                    (dst.data_ptr(), device.index, src_ptr,
+                     desc.device_index, desc.nbytes)
                 )
-                pack_locals[pk] = local
+                out[i] = dst
+        pack_locals: Dict[int, torch.Tensor] = {}
+        for pk in {e[1] for e in pack_entries}:
+            # ONE xGMI copy per pack buffer's used span
+            desc, used = self.pack_descs[pk]
+            local = torch.empty(used, dtype=torch.uint8, device=device)
+            src_ptr = cache.resolve(desc, device.index)
+            copies.append(
+                (local.data_ptr(), device.index, src_ptr,
+                 desc.device_index, used)
+            )
+            pack_locals[pk] = local
         if copies:
             # executor thread: the volume keeps serving other clients while
             # the batched pull runs (the C++ side drops the GIL)
             await asyncio.to_thread(_run_copies, copies)
         if pack_entries:
-            from torchstore_amd.ops import gpu as gpu_ops
-
-            pairs = []
-            for i, pk, off, shape, dtype, prior in pack_entries:
-                local = pack_locals[pk]
-                numel = 1
-                for s in shape:
-                    numel *= s
-                nb = numel * torch._utils._element_size(dtype)
-                slot = local[off : off + nb].view(dtype).reshape(shape)
-                if (
-                    prior is not None
-                    and tuple(prior.shape) == tuple(shape)
-                    and prior.dtype == dtype
-                    and prior.is_contiguous()
-                    and prior.device == device
-                ):
-                    dst = prior
-                else:
-                    dst = torch.empty(shape, dtype=dtype, device=device)
-                pairs.append((slot, dst))
-                out[i] = dst
-            gpu_ops.copy_pairs(pairs, device, blocking=True)
+            self._scatter_packs(pack_entries, pack_locals, device, out)
         return out
+
+    def _scatter_packs(self, pack_entries, pack_locals, device, out) -> None:
+        """One batched K2 scatter splitting the pulled pack buffers into
+        stored tensors."""
+        pairs = []
+        for i, pk, off, shape, dtype, prior in pack_entries:
+            numel = 1
+            for s in shape:
+                numel *= s
+            nb = numel * torch._utils._element_size(dtype)
+            slot = pack_locals[pk][off : off + nb].view(dtype).reshape(shape)
+            dst = _reuse_or_alloc(prior, shape, dtype, device)
+            pairs.append((slot, dst))
+            out[i] = dst
+        _ops()[0].copy_pairs(pairs, device, blocking=True)
 
     # ------------------------------------------------------------- get --
     def _volume_device_index(self) -> int:
@@ -827,39 +867,27 @@ class HipIpcTransportBuffer(TransportBuffer):
                 return 0
         return -1
 
-    async def _stage_get_normal(
-        self,
-        i: int,
-        r: Request,
-        synced: set,
-        gens: Optional[Dict] = None,
-        pull_collect: Optional[List] = None,
-    ) -> Tuple[str, Any]:
-        """Per-request direct staging: export the dest (or a dense scratch),
-        falling back to the windowed path for >=2 GiB blocks."""
+    def _stage_get_normal(self, i, r, synced, gens, pulls) -> Tuple[str, Any]:
+        """Per-request direct staging: export the dest (or a dense scratch);
+        a dest in a >=2 GiB block is queued on ``pulls``."""
         dest = r.tensor_val
         if dest.is_contiguous():
             target = dest
         else:
             target = torch.empty(dest.shape, dtype=dest.dtype, device=dest.device)
             self._scratch[i] = target
-        if target.device.index not in synced:
+        di = target.device.index
+        if di not in synced:
             # pending client kernels touching dest must finish before the
             # volume's one-sided writes land in it
             torch.cuda.current_stream(target.device).synchronize()
-            synced.add(target.device.index)
+            synced.add(di)
         self._hold.append(target)
-        gen = None
-        if gens is not None:
-            di = target.device.index
-            gen = gens.get(di)
-            if gen is None:
-                # one memory_stats call per device per BATCH (it costs
-                # ~100 µs — per-tensor it was 30 ms on a Llama-8B dict)
-                from torchstore_amd.ops import gpu as gpu_ops
-
-                gen = gpu_ops.alloc_generation(di)
-                gens[di] = gen
+        gen = gens.get(di)
+        if gen is None:
+            # one memory_stats call per device per BATCH (it costs
+            # ~100 µs — per-tensor it was 30 ms on a Llama-8B dict)
+            gen = gens[di] = _ops()[0].alloc_generation(di)
         desc = try_export(target, gen)
         if desc is not None:
             return ("ipc", desc)
@@ -868,39 +896,25 @@ class HipIpcTransportBuffer(TransportBuffer):
         # copies it locally; windowed staging only if the volume can't
         # export its side either.  Pulls for one operation batch under a
         # single token (one RPC pair, one copy batch).
-        if pull_collect is not None:
-            pull_collect.append((i, r, target))
-            return ("pending_pull", None)
-        # no collector (direct call): run a one-entry batch immediately
-        single: Dict[int, Tuple[str, Any]] = {}
-        await self._batched_pull([(i, r, target)], single)
-        return single[i]
+        pulls.append((i, r, target))
+        return ("pending_pull", None)
 
-    async def _batched_pull(
-        self,
-        entries: List[Tuple[int, Request, torch.Tensor]],
-        payload,
-    ) -> None:
+    async def _batched_pull(self, entries, payload) -> None:
         """One pull_init / pull_release RPC pair for all entries; entries
         the volume cannot export fall back to the windowed path."""
         volume = self._volume_ref.volume
         cache: IpcOpenCache = self._client_ctx.cache(IpcOpenCache)
         token = uuid.uuid4().hex
         metas = [r.meta_only() for _i, r, _t in entries]
-        descs = await volume.handshake.call_one(
-            self, (token, metas), "pull_init"
-        )
+        descs = await volume.handshake.call_one(self, (token, metas), "pull_init")
         fallback: List[Tuple[int, Request, torch.Tensor]] = []
-        try:
+        async with self._releasing(token, "pull_release", always=True):
             copies = []
             for (i, r, target), desc in zip(entries, descs):
                 if desc is None:
                     fallback.append((i, r, target))
                     continue
-                if (
-                    desc.dtype != target.dtype
-                    or desc.nbytes != target.numel() * target.element_size()
-                ):
+                if desc.dtype != target.dtype or desc.nbytes != _nbytes(target):
                     raise RuntimeError(
                         f"pull mismatch for {r.key}: stored {desc.shape} "
                         f"{desc.dtype} vs dest {tuple(target.shape)} "
@@ -914,27 +928,35 @@ class HipIpcTransportBuffer(TransportBuffer):
                 payload[i] = ("pulled", None)
             if copies:
                 await asyncio.to_thread(_run_copies, copies)
-        finally:
-            try:
-                await volume.handshake.call_one(self, token, "pull_release")
-            except Exception:  # noqa: BLE001
-                pass
         for i, r, target in fallback:
             tok = await self._chunked_get_windows(r, target)
             payload[i] = ("chunked", tok)
 
     async def client_stage_get(self, requests: Sequence[Request]) -> None:
         payload: List[Tuple[str, Any]] = []
-        synced: set = set()
+        synced: set = set()        # devices already synchronised
         gens: Dict[int, int] = {}  # per-device allocator generation, per batch
         pulls: List[Tuple[int, Request, torch.Tensor]] = []
-        vol_dev = self._volume_device_index()
+        direct = (synced, gens, pulls)  # _stage_get_normal's per-batch state
+        bounce_plan = self._classify_get(requests, payload, direct)
+        self.bounce_descs = []
+        self._bounces = []
+        if bounce_plan:
+            self._layout_bounces(requests, bounce_plan, payload, direct)
+        if pulls:
+            await self._batched_pull(pulls, payload)
+        self.payload = payload
+
+    def _classify_get(self, requests, payload, direct):
+        """Fill ``payload`` in request order; returns the bounce plan,
+        (request idx, nbytes) of every entry still waiting for its slot."""
         # cross-device small/strided pieces coalesce through ONE bounce
         # buffer per op: the volume packs them locally (one kernel), moves
         # them with ONE SDMA over xGMI, and the client scatters with one K2
         # launch — instead of a per-piece enqueue storm (the fsdp->tp
         # reshard makes world^2 pieces per step)
-        bounce_plan: List[Tuple[int, int]] = []  # (request idx, nbytes)
+        bounce_plan: List[Tuple[int, int]] = []
+        vol_dev = self._volume_device_index()
         for i, r in enumerate(requests):
             if r.is_object:
                 payload.append(("fetch_obj", None))
@@ -945,74 +967,53 @@ class HipIpcTransportBuffer(TransportBuffer):
             if dest.device.type != "cuda":
                 payload.append(("fetch_inline", None))
                 continue
-            nbytes = dest.numel() * dest.element_size()
+            nbytes = _nbytes(dest)
             cross = vol_dev >= 0 and vol_dev != dest.device.index
             if cross and (not dest.is_contiguous() or nbytes < (32 << 20)):
-                payload.append(("bounce", None))  # offsets assigned below
+                payload.append(("bounce", None))  # slot: _layout_bounces
                 bounce_plan.append((i, nbytes))
                 continue
-            payload.append(
-                await self._stage_get_normal(i, r, synced, gens, pulls)
-            )
+            payload.append(self._stage_get_normal(i, r, *direct))
+        return bounce_plan
 
-        self.bounce_descs: List[IpcDescriptor] = []
-        self._bounces: List[torch.Tensor] = []
-        if bounce_plan:
-            device = requests[bounce_plan[0][0]].tensor_val.device
-            cap = 1 << 30  # each bounce buffer stays well under the 2GiB limit
-            aligned = [(i, n, (n + 255) & ~255) for i, n in bounce_plan]
-            # a single piece larger than the cap can never fit a bounce
-            # reservation — stage it directly (scratch + windowed path)
-            oversized = [e for e in aligned if e[2] > cap]
-            aligned = [e for e in aligned if e[2] <= cap]
-            for i, _n, _a in oversized:
-                payload[i] = await self._stage_get_normal(
-                    i, requests[i], synced, gens, pulls
-                )
-            remaining = sum(a for _, _, a in aligned)
-            off = 0
-            size = 0
-            b_idx = -1
-            ok = True
-            for i, nbytes, a in aligned:
-                if b_idx < 0 or off + a > size:
-                    size = min(cap, max(remaining, a))
-                    buf = torch.empty(size, dtype=torch.uint8, device=device)
-                    desc_b = try_export(buf)
-                    if desc_b is None:
-                        # the bounce itself landed in a >=2 GiB cached block:
-                        # degrade to per-request staging instead of failing
-                        ok = False
-                        break
-                    self._bounces.append(buf)
-                    self._hold.append(buf)
-                    self.bounce_descs.append(desc_b)
-                    b_idx += 1
-                    off = 0
-                payload[i] = ("bounce", (b_idx, off, nbytes))
-                off += a
-                remaining -= a
-            if not ok:
+    def _layout_bounces(self, requests, bounce_plan, payload, direct):
+        """Allocate and export the bounce buffers and give each planned entry
+        its slot; an unexportable bounce degrades them all to per-request
+        staging."""
+        device = requests[bounce_plan[0][0]].tensor_val.device
+        cap = self.BOUNCE_BUF_CAP
+        # a single piece larger than the cap can never fit a bounce
+        # reservation — stage it directly (scratch + windowed path)
+        fits = [e for e in bounce_plan if _aligned(e[1]) <= cap]
+        for i, n in bounce_plan:
+            if _aligned(n) > cap:
+                payload[i] = self._stage_get_normal(i, requests[i], *direct)
+        slots, buffers = _plan_slots([n for _i, n in fits], cap)
+        for size, _used in buffers:
+            buf = torch.empty(size, dtype=torch.uint8, device=device)
+            desc = try_export(buf)
+            if desc is None:
+                # the bounce itself landed in a >=2 GiB cached block:
+                # degrade to per-request staging instead of failing
                 self._bounces = []
                 self.bounce_descs = []
-                for i, nbytes, a in aligned:
-                    payload[i] = await self._stage_get_normal(
-                        i, requests[i], synced, gens, pulls
-                    )
-            elif device.index not in synced:
-                torch.cuda.current_stream(device).synchronize()
-        if pulls:
-            await self._batched_pull(pulls, payload)
-        self.payload = payload
+                for i, _n in fits:
+                    payload[i] = self._stage_get_normal(i, requests[i], *direct)
+                return
+            self._bounces.append(buf)
+            self._hold.append(buf)
+            self.bounce_descs.append(desc)
+        for (i, n), (b, off) in zip(fits, slots):
+            payload[i] = ("bounce", (b, off, n))
+        if device.index not in direct[0]:  # synced
+            torch.cuda.current_stream(device).synchronize()
 
     async def volume_send(self, requests, values):
         cache: IpcOpenCache = self._volume_ctx.cache(IpcOpenCache)
         chunks: ChunkStagingCache = self._volume_ctx.cache(ChunkStagingCache)
-        from torchstore_amd.ops import gpu as gpu_ops
-
         reply: List[Tuple[str, Any]] = []
         fused: List[Tuple[torch.Tensor, int]] = []   # same-device: K1 writes
-        copies: List[Tuple[int, int, int, int, int]] = []  # cross-device SDMA
+        copies: List[Copy] = []                      # cross-device SDMA
         copies_2d: List[Tuple[int, int, int, int, int, int, int, int]] = []
         # bounce coalescing: b_idx -> (staging tensor, pack pairs, used bytes)
         bounce_state: Dict[int, Tuple[torch.Tensor, list, int]] = {}
@@ -1022,131 +1023,141 @@ class HipIpcTransportBuffer(TransportBuffer):
                 reply.append(("inline", v))
                 continue
             if v.device.type != "cuda" and kind in ("ipc", "bounce"):
-                # tier-spilled (host-resident) value headed for a GPU dest:
-                # stage through HBM and take the one-sided path — the
-                # inline-RPC serialization ran at ~2 GB/s, a pinned H2D +
-                # device copy at ~40 GB/s
-                if torch.cuda.is_available():
-                    v = v.to(
-                        torch.device("cuda", torch.cuda.current_device()),
-                        non_blocking=False,
-                    )
+                v = self._spill_to_hbm(v)
             if kind == "fetch_inline" or v.device.type != "cuda":
                 reply.append(("inline", v))
-                continue
-            if kind == "chunked":
+            elif kind == "chunked":
                 # windows already delivered during the handshake phases
                 chunks.release(value)
                 reply.append(("done", None))
-                continue
-            if kind == "pulled":
+            elif kind == "pulled":
                 # the client already copied out of the pinned export
                 reply.append(("done", None))
-                continue
-            if kind == "bounce":
-                b_idx, off, want_bytes = value
-                bdesc = self.bounce_descs[b_idx]
+            elif kind == "bounce":
                 device = v.device
-                nbytes = v.numel() * v.element_size()
-                if nbytes != want_bytes or off + nbytes > bdesc.nbytes:
-                    raise RuntimeError(
-                        f"bounce size mismatch for {r.key}: stored {nbytes} "
-                        f"vs reserved {want_bytes} at {off}/{bdesc.nbytes}"
-                    )
-                entry = bounce_state.get(b_idx)
-                if entry is None:
-                    staging = torch.empty(
-                        bdesc.nbytes, dtype=torch.uint8, device=v.device
-                    )
-                    entry = (staging, [], 0)
-                staging, pairs, used = entry
-                slot = (
-                    staging[off : off + nbytes]
-                    .view(v.dtype)
-                    .reshape(v.shape)
-                )
-                pairs.append((v, slot))
-                bounce_state[b_idx] = (staging, pairs, max(used, off + nbytes))
+                self._reserve_bounce(r, v, value, bounce_state)
                 reply.append(("bounced", None))
-                continue
-            desc: IpcDescriptor = value
-            device = v.device
-            if v.numel() * v.element_size() != desc.nbytes:
-                raise RuntimeError(
-                    f"get size mismatch for {r.key}: stored {tuple(v.shape)} "
-                    f"vs dest {desc.shape}"
-                )
-            if v.dtype != desc.dtype:
-                raise TypeError(
-                    f"get dtype mismatch for {r.key}: stored {v.dtype} vs "
-                    f"dest {desc.dtype} — raw one-sided copies cannot cast; "
-                    "fetch at the stored dtype and cast locally"
-                )
-            dst_ptr = cache.resolve(desc, v.device.index)
-            if desc.device_index == v.device.index:
-                # co-located: the K1 gather kernel writes STRAIGHT into the
-                # client's mapped destination — no packed intermediate
-                fused.append((v, dst_ptr))
-            else:
-                # cross-device (over xGMI): large 2-D strided sources go
-                # through one SDMA pitched read — still no packed
-                # intermediate; only irregular layouts pack first
-                sp = (
-                    gpu_ops._pitched_params(v)
-                    if desc.nbytes >= gpu_ops._SDMA_2D_MIN_BYTES
-                    and not v.is_contiguous()
-                    else None
-                )
-                if sp is not None:
-                    copies_2d.append(
-                        (dst_ptr, v.device.index, sp[1],
-                         v.data_ptr(), v.device.index, sp[0], sp[1], sp[2])
-                    )
-                else:
-                    vc = gpu_ops.pack_region(v)  # K1 gather for strided views
-                    copies.append(
-                        (dst_ptr, desc.device_index, vc.data_ptr(),
-                         v.device.index, desc.nbytes)
-                    )
-                    self._hold.append(vc)
-            reply.append(("done", None))
+            else:  # "ipc"
+                device = v.device
+                self._route_direct(r, v, value, cache, fused, copies, copies_2d)
+                reply.append(("done", None))
         if fused:
             # executor thread: loop stays responsive; kernel runs on the
             # device's default stream and is synchronized before return
             rejects = await asyncio.to_thread(
-                gpu_ops.copy_views_to_ptrs, fused, device, True
+                _ops()[0].copy_views_to_ptrs, fused, device, True
             )
-            for v, dst_ptr in rejects:  # kernel-inexpressible layout
-                vc = gpu_ops.pack_region(v)
-                copies.append(
-                    (dst_ptr, device.index, vc.data_ptr(), device.index,
-                     vc.numel() * vc.element_size())
-                )
-                self._hold.append(vc)
+            self._pack_fused_rejects(rejects, device, copies)
         if bounce_state:
-            # pack ALL bounce pieces with one batched K1 launch, then move
-            # each bounce with ONE SDMA over xGMI into client memory
-            all_pairs = []
-            for staging, pairs, used in bounce_state.values():
-                all_pairs.extend(pairs)
-                self._hold.append(staging)
-            gpu_ops.copy_pairs(all_pairs, device, blocking=False)
-            for b_idx, (staging, _pairs, used) in bounce_state.items():
-                bdesc = self.bounce_descs[b_idx]
-                remote = cache.resolve(bdesc, device.index)
-                copies.append(
-                    (remote, bdesc.device_index, staging.data_ptr(),
-                     device.index, used)
-                )
-        if copies or copies_2d:
-            if copies:
-                # pack kernels ran on the current stream; the pool streams
-                # used by copy_batch must observe their writes
-                torch.cuda.current_stream(device).synchronize()
-                await asyncio.to_thread(_run_copies, copies)
-            if copies_2d:
-                await asyncio.to_thread(_ext().copy_batch_2d, copies_2d)
+            self._pack_bounces(bounce_state, cache, device, copies)
+        if copies:
+            # pack kernels ran on the current stream; the pool streams
+            # used by copy_batch must observe their writes
+            torch.cuda.current_stream(device).synchronize()
+            await asyncio.to_thread(_run_copies, copies)
+        if copies_2d:
+            await asyncio.to_thread(_ext().copy_batch_2d, copies_2d)
         return reply
+
+    @staticmethod
+    def _spill_to_hbm(v: torch.Tensor) -> torch.Tensor:
+        """A tier-spilled (host-resident) value headed for a GPU dest stages
+        through HBM and takes the one-sided path — the inline-RPC
+        serialization ran at ~2 GB/s, a pinned H2D + device copy at ~40."""
+        if torch.cuda.is_available():
+            v = v.to(torch.device("cuda", torch.cuda.current_device()))
+        return v
+
+    def _pack_fused_rejects(self, rejects, device, copies) -> None:
+        """Layouts the fused kernel cannot express: pack, then batch-copy."""
+        for v, dst_ptr in rejects:
+            vc = _ops()[0].pack_region(v)
+            copies.append(
+                (dst_ptr, device.index, vc.data_ptr(), device.index,
+                 _nbytes(vc))
+            )
+            self._hold.append(vc)
+
+    def _reserve_bounce(self, r, v, value, bounce_state) -> None:
+        """Queue ``v`` for the pack into its slot of the volume-local twin of
+        the client's bounce buffer (allocated at the buffer's first entry)."""
+        b_idx, off, want_bytes = value
+        bdesc = self.bounce_descs[b_idx]
+        nbytes = _nbytes(v)
+        if nbytes != want_bytes or off + nbytes > bdesc.nbytes:
+            raise RuntimeError(
+                f"bounce size mismatch for {r.key}: stored {nbytes} "
+                f"vs reserved {want_bytes} at {off}/{bdesc.nbytes}"
+            )
+        entry = bounce_state.get(b_idx)
+        if entry is None:
+            staging = torch.empty(bdesc.nbytes, dtype=torch.uint8, device=v.device)
+            entry = (staging, [], 0)
+        staging, pairs, used = entry
+        slot = staging[off : off + nbytes].view(v.dtype).reshape(v.shape)
+        pairs.append((v, slot))
+        bounce_state[b_idx] = (staging, pairs, max(used, off + nbytes))
+
+    def _route_direct(
+        self, r, v, desc: IpcDescriptor, cache, fused, copies, copies_2d
+    ) -> None:
+        """Check ``v`` against the client's exported dest and queue it on the
+        cheapest mover."""
+        gpu_ops = _ops()[0]
+        if _nbytes(v) != desc.nbytes:
+            raise RuntimeError(
+                f"get size mismatch for {r.key}: stored {tuple(v.shape)} "
+                f"vs dest {desc.shape}"
+            )
+        if v.dtype != desc.dtype:
+            raise TypeError(
+                f"get dtype mismatch for {r.key}: stored {v.dtype} vs "
+                f"dest {desc.dtype} — raw one-sided copies cannot cast; "
+                "fetch at the stored dtype and cast locally"
+            )
+        dst_ptr = cache.resolve(desc, v.device.index)
+        if desc.device_index == v.device.index:
+            # co-located: the K1 gather kernel writes STRAIGHT into the
+            # client's mapped destination — no packed intermediate
+            fused.append((v, dst_ptr))
+            return
+        # cross-device (over xGMI): large 2-D strided sources go through
+        # one SDMA pitched read — still no packed intermediate; only
+        # irregular layouts pack first
+        sp = (
+            gpu_ops._pitched_params(v)
+            if desc.nbytes >= gpu_ops._SDMA_2D_MIN_BYTES
+            and not v.is_contiguous()
+            else None
+        )
+        if sp is not None:
+            copies_2d.append(
+                (dst_ptr, v.device.index, sp[1],
+                 v.data_ptr(), v.device.index, sp[0], sp[1], sp[2])
+            )
+        else:
+            vc = gpu_ops.pack_region(v)  # K1 gather for strided views
+            copies.append(
+                (dst_ptr, desc.device_index, vc.data_ptr(),
+                 v.device.index, desc.nbytes)
+            )
+            self._hold.append(vc)
+
+    def _pack_bounces(self, bounce_state, cache, device, copies) -> None:
+        """Pack ALL bounce pieces with one batched K1 launch, then queue ONE
+        SDMA over xGMI per bounce into client memory."""
+        all_pairs = []
+        for staging, pairs, _used in bounce_state.values():
+            all_pairs.extend(pairs)
+            self._hold.append(staging)
+        _ops()[0].copy_pairs(all_pairs, device, blocking=False)
+        for b_idx, (staging, _pairs, used) in bounce_state.items():
+            bdesc = self.bounce_descs[b_idx]
+            remote = cache.resolve(bdesc, device.index)
+            copies.append(
+                (remote, bdesc.device_index, staging.data_ptr(),
+                 device.index, used)
+            )
 
     def client_complete_get(self, requests, reply) -> List[Any]:
         out: List[Any] = []
@@ -1163,9 +1174,8 @@ class HipIpcTransportBuffer(TransportBuffer):
             if kind == "bounced":
                 b_idx, off, _nb = self.payload[i][1]
                 dest = r.tensor_val
-                nbytes = dest.numel() * dest.element_size()
                 piece = (
-                    self._bounces[b_idx][off : off + nbytes]
+                    self._bounces[b_idx][off : off + _nbytes(dest)]
                     .view(dest.dtype)
                     .reshape(dest.shape)
                 )
@@ -1180,9 +1190,7 @@ class HipIpcTransportBuffer(TransportBuffer):
             out.append(r.tensor_val)
         if scatter_pairs:
             # K2: one batched scatter kernel for every strided destination
-            from torchstore_amd.ops import gpu as gpu_ops
-
-            gpu_ops.copy_pairs(scatter_pairs, device, blocking=False)
+            _ops()[0].copy_pairs(scatter_pairs, device, blocking=False)
         return out
 
     async def drop(self) -> None:
