@@ -26,6 +26,8 @@ def test_extension_loads_natively():
         (torch.bfloat16, torch.float32),
         (torch.float32, torch.float16),
         (torch.float16, torch.float32),
+        (torch.bfloat16, torch.float16),
+        (torch.float16, torch.bfloat16),
     ],
 )
 def test_cast_copy_matches_torch(src_dtype, dst_dtype):

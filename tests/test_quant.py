@@ -115,14 +115,10 @@ def test_cpu_quant_matches_oracle(shape, dtype):
 def test_cpu_zero_and_tiny_blocks(dtype):
     """An all-zero block quantises to zeros with the floor scale; a block
     whose amax lies below 2**-96 is scaled by the floor, not by its amax."""
+    from tests.value_grids import zero_and_tiny_blocks
     from torchstore_amd.ops import quant
 
-    x = make_input((3, 384), torch.float32)
-    x[1, 128:256] = 0.0
-    tiny = 2.0 ** -100 if dtype != torch.float16 else 0.0
-    x[2, 0:128] = tiny
-    x[2, 5] = -tiny
-    x = x.to(dtype)
+    x = zero_and_tiny_blocks(dtype)
     (pair,) = quant.quantize_fp8([x])
     assert_pair_matches(pair, x)
     payload, scales = pair

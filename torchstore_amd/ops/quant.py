@@ -15,7 +15,12 @@ Every step is one correctly rounded IEEE operation, so the HIP kernels
 (``csrc/quant_fp8.h``, one launch per call over all CUDA tensors of a device)
 and the pure-torch implementation below (the path for CPU tensors) produce
 the same bytes.  Non-finite inputs are outside the contract: a NaN or Inf
-poisons the payload and scale of its own block, nothing else.
+poisons the payload and scale of its own block, nothing else.  Quantising
+finite input never produces the two NaN codes (``0x7F``, ``0xFF``); a payload
+that holds one anyway dequantises to NaN there (payload and sign unspecified)
+and is exact everywhere else.  The product overflows and underflows as IEEE
+says: ``inf`` in an f16 output where ``float(q) * scale`` exceeds its range,
+subnormals where it falls below, and a zero keeps the sign of ``q``.
 """
 
 from __future__ import annotations
