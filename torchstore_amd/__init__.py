@@ -32,9 +32,10 @@ from torchstore_amd.api import (
     shutdown,
     stats,
 )
+from torchstore_amd.ops.mx import MxQuantizedTensor
 from torchstore_amd.ops.quant import QuantizedTensor
 from torchstore_amd.spmd import SPMDEnv, initialize_spmd, shutdown_spmd
-from torchstore_amd.state_dict import Fp8BlockQuant
+from torchstore_amd.state_dict import Fp8BlockQuant, Mxfp4BlockQuant
 from torchstore_amd.strategy import (
     HostStrategy,
     LocalRankStrategy,
@@ -76,6 +77,8 @@ __all__ = [
     "SingletonStrategy",
     "TransportType",
     "Fp8BlockQuant",
+    "Mxfp4BlockQuant",
+    "MxQuantizedTensor",
     "QuantizedTensor",
     "LocalShard",
     "Request",

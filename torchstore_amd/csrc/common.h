@@ -43,6 +43,7 @@
 //   HIPSTORE_CAST_V       8                      >= 1; 16 and above run the
 //                                                16-element kernel
 //   HIPSTORE_QUANT_GRID   65536                  >= 64
+//   HIPSTORE_MX_GRID      65536                  >= 64
 //
 // The measurements behind each default stand next to the code that uses it.
 

@@ -26,6 +26,9 @@
 //   * quant_fp8_batch / dequant_fp8_batch (quant_fp8.h) — K4/K5: block-scaled
 //     FP8 (OCP e4m3, 128-element blocks, f32 scales) over N tensors in one
 //     launch each way, bit-exact against the torch recipe.
+//   * quant_mx_batch / dequant_mx_batch (quant_mx.h) — K6/K7: MXFP4 (packed
+//     OCP e2m1, 32-element blocks, e8m0 scale bytes) the same way, with a
+//     launch counter of their own.
 //   * host_register / host_unregister — pin SHM pages for DMA.
 // Underneath: plan.h turns the python tuples into descriptors (HIP-free; also
 // built on the CPU by tests/native/plan_check.cpp), desc_ring.h stages them
@@ -44,6 +47,7 @@
 #include "ipc.h"
 #include "plan.h"
 #include "quant_fp8.h"
+#include "quant_mx.h"
 
 #include <pybind11/pybind11.h>
 #include <pybind11/stl.h>
@@ -170,6 +174,20 @@ static void quant_fp8_batch(const std::vector<PyQuantItem>& items, int device,
                             reinterpret_cast<hipStream_t>(stream_handle));
 }
 
+// K6/K7; the same tuples, scales being e8m0 bytes
+template <bool DEQUANT>
+static void quant_mx_batch(const std::vector<PyQuantItem>& items, int device,
+                           uintptr_t stream_handle) {
+  std::vector<QuantIn> in;
+  in.reserve(items.size());
+  for (const auto& it : items) {
+    const auto& [wide, payload, scales, rows, cols, dtype] = it;
+    in.push_back(QuantIn{wide, payload, scales, rows, cols, dtype});
+  }
+  launch_quant_mx<DEQUANT>(plan_mx(in), device,
+                           reinterpret_cast<hipStream_t>(stream_handle));
+}
+
 // host pinning and staging
 
 // single UVA-resolved copy on a dedicated pool stream (blocking).  Used by
@@ -237,6 +255,17 @@ PYBIND11_MODULE(_hipstore, m) {
     return g_quant_launches.load(std::memory_order_relaxed);
   });
   m.attr("QUANT_BLOCK") = kQuantBlock;
+  m.def("quant_mx_batch", &quant_mx_batch<false>, py::arg("items"),
+        py::arg("device"), py::arg("stream"),
+        py::call_guard<py::gil_scoped_release>());
+  m.def("dequant_mx_batch", &quant_mx_batch<true>, py::arg("items"),
+        py::arg("device"), py::arg("stream"),
+        py::call_guard<py::gil_scoped_release>());
+  m.def("mx_launches", []() {
+    return g_mx_launches.load(std::memory_order_relaxed);
+  });
+  m.attr("MX_BLOCK") = kMxBlock;
+  m.attr("MX_LANES") = kMxLanes;
   m.def("sdma_copy", &sdma_copy, py::arg("dst"), py::arg("src"),
         py::arg("nbytes"), py::arg("device"),
         py::call_guard<py::gil_scoped_release>());

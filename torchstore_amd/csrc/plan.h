@@ -21,6 +21,12 @@ static constexpr uint32_t kQuantBlock = 128;
 static constexpr uint32_t kQuantPasses = 2;
 static constexpr uint32_t kQuantUnitBlocks = 32 * kQuantPasses;
 
+// MXFP4: 32-element blocks (OCP Microscaling); a unit is one pass of a
+// 256-thread workgroup with a block per lane, or two with a block per lane
+// pair, so its size does not depend on how quant_mx.h lays the lanes out
+static constexpr uint32_t kMxBlock = 32;
+static constexpr uint32_t kMxUnitBlocks = 256;
+
 // descriptors (read by the kernels; every one carries the exclusive prefix
 // sum of units that unit_walk.h searches)
 
@@ -69,6 +75,22 @@ struct QuantDesc {
   uint32_t pad_;
 };
 static_assert(sizeof(QuantDesc) == 64, "QuantDesc is meant to be 64 bytes");
+
+// K6/K7: unit = kMxUnitBlocks consecutive 32-element blocks of a tensor
+struct MxDesc {
+  uintptr_t wide;         // f32/bf16/f16 tensor: quant source, dequant dest
+  uintptr_t payload;      // packed e2m1, rows of ceil(cols / 2) bytes
+  uintptr_t scales;       // e8m0 bytes [rows, nblk]
+  uint64_t rows;
+  uint64_t units_prefix;  // exclusive prefix sum of units
+  uint32_t cols;
+  uint32_t nblk;          // blocks per row = ceil(cols / 32)
+  uint32_t nblocks;       // rows * nblk
+  uint32_t dtype;         // DType code of `wide` (0 = f32, 1 = f16, 2 = bf16)
+  uint32_t fast;          // 1 = 16B-vector path (block b sits at element 32 b)
+  uint32_t pad_;
+};
+static_assert(sizeof(MxDesc) == 64, "MxDesc is meant to be 64 bytes");
 
 template <typename Desc>
 struct Plan {
@@ -193,6 +215,34 @@ inline Plan<QuantDesc> plan_quant(const std::vector<QuantIn>& in) {
                                 p.units, (uint32_t)it.cols, (uint32_t)nblk,
                                 (uint32_t)nblocks, (uint32_t)it.dtype, fast, 0});
     p.units += (nblocks + kQuantUnitBlocks - 1) / kQuantUnitBlocks;
+  }
+  return p;
+}
+
+// MXFP4 quant / dequant plan, from the same tuples as plan_quant (the scales
+// are bytes here, so they need no alignment); tensors with no elements are
+// dropped.  Fast needs whole blocks only: then rows never end inside a block
+// or a payload byte, and block b of the tensor is elements [32 b, 32 b + 32).
+inline Plan<MxDesc> plan_mx(const std::vector<QuantIn>& in) {
+  Plan<MxDesc> p;
+  p.descs.reserve(in.size());
+  for (const QuantIn& it : in) {
+    if (it.dtype < 0 || it.dtype > 2)
+      throw std::runtime_error("unsupported dtype");
+    if (it.rows == 0 || it.cols == 0) continue;
+    const uint64_t nblk = (it.cols + kMxBlock - 1) / kMxBlock;
+    const uint64_t nblocks = it.rows * nblk;
+    if (it.cols > UINT32_MAX || nblocks > (1ull << 31))
+      throw std::runtime_error("tensor too large for one mx descriptor");
+    const uint32_t es = it.dtype == 0 ? 4u : 2u;
+    if (it.wide % es) throw std::runtime_error("misaligned tensor");
+    const uint32_t fast =
+        (((it.wide | it.payload) & 15u) == 0 && it.cols % kMxBlock == 0) ? 1u
+                                                                        : 0u;
+    p.descs.push_back(MxDesc{it.wide, it.payload, it.scales, it.rows, p.units,
+                             (uint32_t)it.cols, (uint32_t)nblk,
+                             (uint32_t)nblocks, (uint32_t)it.dtype, fast, 0});
+    p.units += (nblocks + kMxUnitBlocks - 1) / kMxUnitBlocks;
   }
   return p;
 }

@@ -5,6 +5,7 @@ The extension is built in-tree for gfx950 (``python setup.py build_ext
 
 * K1 slice-gather / K2 batched multi-slice-scatter / K3 fused cast kernels;
 * K4/K5 batched block-scaled FP8 quantise / dequantise kernels;
+* K6/K7 batched MXFP4 (packed e2m1 + e8m0 block scales) kernels;
 * HIP IPC: export/open ``hipIpcMemHandle_t``, batched peer copies on
   dedicated streams, event completion;
 * host page pinning (``hipHostRegister``) for the SHM transport.
@@ -101,7 +102,7 @@ def cast_copy(src: torch.Tensor, out: torch.Tensor) -> None:
     )
 
 
-def _quant_items(triples):
+def _quant_items(triples, what="fp8"):
     items = []
     for wide, payload, scales in triples:
         if not (
@@ -109,7 +110,7 @@ def _quant_items(triples):
             and payload.is_contiguous()
             and scales.is_contiguous()
         ):
-            raise ValueError("fp8 quant kernels require contiguous tensors")
+            raise ValueError(f"{what} quant kernels require contiguous tensors")
         cols = wide.shape[-1]
         rows = wide.numel() // cols if cols else 0
         items.append(
@@ -136,6 +137,29 @@ def dequant_fp8_batch(triples, device: torch.device) -> None:
 def quant_launches() -> int:
     """Launches of K4 + K5 so far (tests observe the batching with it)."""
     return ext().quant_launches()
+
+
+def quant_mx_batch(triples, device: torch.device) -> None:
+    """K6: ``[(src, payload, scales), ...]`` — MXFP4 quantise of N tensors
+    in ONE launch on the caller's current stream (async).  ``payload`` and
+    ``scales`` are the uint8 buffers of ``ops.mx.mx_shapes(src.shape)``."""
+    ext().quant_mx_batch(
+        _quant_items(triples, "mxfp4"), device.index, _stream(device)
+    )
+
+
+def dequant_mx_batch(triples, device: torch.device) -> None:
+    """K7: ``[(dst, payload, scales), ...]`` — the mirror image of K6; the
+    destination's shape is the logical one and its dtype (f32/bf16/f16)
+    decides the output rounding."""
+    ext().dequant_mx_batch(
+        _quant_items(triples, "mxfp4"), device.index, _stream(device)
+    )
+
+
+def mx_launches() -> int:
+    """Launches of K6 + K7 so far (counted apart from K4/K5)."""
+    return ext().mx_launches()
 
 
 # a contiguous source below this many bytes is ONE flat descriptor; the

@@ -73,17 +73,10 @@ def scales_shape(shape: Sequence[int]) -> Tuple[int, ...]:
     return shape[:-1] + ((shape[-1] + BLOCK - 1) // BLOCK,)
 
 
-def alloc_quantized(
-    shapes: Sequence[Sequence[int]], device: torch.device
-) -> List[Tuple[torch.Tensor, torch.Tensor]]:
-    """Uninitialised ``(payload, scales)`` buffers for tensors of ``shapes``
-    on ``device``, every buffer contiguous and at least 16 B aligned."""
-    pieces = []  # (nbytes, dtype, shape) in output order: payload, scales, ...
-    for shape in shapes:
-        shape = tuple(shape)
-        sshape = scales_shape(shape)
-        pieces.append((_numel(shape), FP8_DTYPE, shape))
-        pieces.append((_numel(sshape) * 4, torch.float32, sshape))
+def carve_slabs(pieces, device: torch.device) -> List[torch.Tensor]:
+    """One uninitialised contiguous buffer per ``(nbytes, dtype, shape)``
+    piece, carved in order from shared slabs at 256 B boundaries; a piece of
+    slab size or more, or of no bytes, gets an allocation of its own."""
     bufs: List[torch.Tensor] = [None] * len(pieces)
     group: List[Tuple[int, int]] = []  # (piece index, offset) of the open slab
     used = 0
@@ -106,6 +99,21 @@ def alloc_quantized(
         group.append((i, used))
         used += (nbytes + _ALIGN - 1) // _ALIGN * _ALIGN
     close()
+    return bufs
+
+
+def alloc_quantized(
+    shapes: Sequence[Sequence[int]], device: torch.device
+) -> List[Tuple[torch.Tensor, torch.Tensor]]:
+    """Uninitialised ``(payload, scales)`` buffers for tensors of ``shapes``
+    on ``device``, every buffer contiguous and at least 16 B aligned."""
+    pieces = []  # (nbytes, dtype, shape) in output order: payload, scales, ...
+    for shape in shapes:
+        shape = tuple(shape)
+        sshape = scales_shape(shape)
+        pieces.append((_numel(shape), FP8_DTYPE, shape))
+        pieces.append((_numel(sshape) * 4, torch.float32, sshape))
+    bufs = carve_slabs(pieces, device)
     return [(bufs[2 * j], bufs[2 * j + 1]) for j in range(len(shapes))]
 
 

@@ -19,6 +19,10 @@ staging copy and the cast are one kernel pass.
 scales under ``"{key}/<FP8_SCALES>/{flat_key}"``, and the commit marker —
 a :class:`QuantMapping` — records which flat keys are quantised and their
 original dtype, so readers learn it from the fetch they already make.
+``transfer_quant="mxfp4"`` does the same with MXFP4 (``ops/mx.py``): scales
+under ``"{key}/<MX_SCALES>/{flat_key}"``, and the marker's ``mx`` field
+records the original dtype and the logical shape (an odd last dimension
+cannot be told from the packed payload).  A push uses one policy.
 """
 
 from __future__ import annotations
@@ -32,6 +36,13 @@ from typing import Any, Dict, List, Optional, Sequence, Tuple, Union
 import torch
 
 from torchstore_amd.client import LocalClient
+from torchstore_amd.ops.mx import (
+    MxQuantizedTensor,
+    alloc_mx,
+    dequantize_mxfp4_into,
+    mx_shapes,
+    quantize_mxfp4,
+)
 from torchstore_amd.ops.quant import (
     QUANT_DTYPES,
     QuantizedTensor,
@@ -48,6 +59,18 @@ MAPPING_KEY = "<MAPPING>"
 # scales of quantised entries live under this reserved segment, next to
 # <MAPPING>: a flat key never starts with an angle-bracket segment of ours
 SCALES_KEY = "<FP8_SCALES>"
+MX_SCALES_KEY = "<MX_SCALES>"
+_SCALES_KEYS = (SCALES_KEY, MX_SCALES_KEY)
+
+
+def _selects(policy, flat_key: str, value: Any) -> bool:
+    return (
+        type(value) is torch.Tensor
+        and value.dtype in QUANT_DTYPES
+        and value.dim() >= 1
+        and value.numel() >= policy.min_numel
+        and not any(fnmatch.fnmatchcase(flat_key, p) for p in policy.exclude)
+    )
 
 
 @dataclass(frozen=True)
@@ -64,40 +87,65 @@ class Fp8BlockQuant:
     exclude: Sequence[str] = ()
 
     def selects(self, flat_key: str, value: Any) -> bool:
-        return (
-            type(value) is torch.Tensor
-            and value.dtype in QUANT_DTYPES
-            and value.dim() >= 1
-            and value.numel() >= self.min_numel
-            and not any(fnmatch.fnmatchcase(flat_key, p) for p in self.exclude)
-        )
+        return _selects(self, flat_key, value)
+
+
+@dataclass(frozen=True)
+class Mxfp4BlockQuant:
+    """``transfer_quant`` policy: MXFP4, packed e2m1 values with one e8m0
+    scale byte per block of 32 (``ops/mx.py``).  Selects entries by the same
+    rule as :class:`Fp8BlockQuant`."""
+
+    min_numel: int = 0
+    exclude: Sequence[str] = ()
+
+    def selects(self, flat_key: str, value: Any) -> bool:
+        return _selects(self, flat_key, value)
+
+
+TransferQuant = Union[None, str, Fp8BlockQuant, Mxfp4BlockQuant]
 
 
 def _resolve_quant(
-    transfer_quant: Union[None, str, Fp8BlockQuant]
-) -> Optional[Fp8BlockQuant]:
-    if transfer_quant is None or isinstance(transfer_quant, Fp8BlockQuant):
+    transfer_quant: TransferQuant,
+) -> Union[None, Fp8BlockQuant, Mxfp4BlockQuant]:
+    if transfer_quant is None or isinstance(
+        transfer_quant, (Fp8BlockQuant, Mxfp4BlockQuant)
+    ):
         return transfer_quant
     if transfer_quant == "fp8_e4m3":
         return Fp8BlockQuant()
+    if transfer_quant == "mxfp4":
+        return Mxfp4BlockQuant()
     raise ValueError(
-        f"unknown transfer_quant {transfer_quant!r}: expected 'fp8_e4m3' or "
-        "an Fp8BlockQuant"
+        f"unknown transfer_quant {transfer_quant!r}: expected 'fp8_e4m3', "
+        "'mxfp4', an Fp8BlockQuant or an Mxfp4BlockQuant"
     )
 
 
 class QuantMapping(dict):
     """The commit marker of a quantised push: the usual flat-key mapping plus
-    ``quant``, ``{flat_key: original dtype}`` of the quantised entries.  A
-    plain push keeps writing a plain dict, so readers tell the two apart
-    from the marker they fetch anyway."""
+    ``quant``, ``{flat_key: original dtype}`` of the FP8 entries, or ``mx``,
+    ``{flat_key: (original dtype, logical shape)}`` of the MXFP4 ones.  A
+    plain push keeps writing a plain dict, so readers tell them apart from
+    the marker they fetch anyway."""
 
-    def __init__(self, mapping=(), quant: Optional[Dict[str, torch.dtype]] = None):
+    def __init__(
+        self,
+        mapping=(),
+        quant: Optional[Dict[str, torch.dtype]] = None,
+        mx: Optional[Dict[str, Tuple[torch.dtype, Tuple[int, ...]]]] = None,
+    ):
         super().__init__(mapping)
         self.quant = dict(quant or {})
+        self.mx = dict(mx or {})
 
     def __reduce__(self):
-        return (QuantMapping, (dict(self), self.quant))
+        # without MXFP4 entries the marker pickles as it did before they
+        # existed: plain and FP8 pushes stay byte-identical on the wire
+        if not self.mx:
+            return (QuantMapping, (dict(self), self.quant))
+        return (QuantMapping, (dict(self), self.quant, self.mx))
 
 # pipeline factor: big state_dicts move as N concurrent sub-batches so RPC
 # framing/parsing overlaps the volume's bulk copies
@@ -165,9 +213,10 @@ def _scales_beside_payloads(
     out: Dict[str, Any] = {}
     for k in flat_keys:
         out[f"{key}/{k}"] = fetches[f"{key}/{k}"]
-        sk = f"{key}/{SCALES_KEY}/{k}"
-        if sk in fetches:
-            out[sk] = fetches[sk]
+        for scales_key in _SCALES_KEYS:
+            sk = f"{key}/{scales_key}/{k}"
+            if sk in fetches:
+                out[sk] = fetches[sk]
     return out
 
 
@@ -221,6 +270,59 @@ def _plan_quant_dests(
     return pending
 
 
+def _plan_mx_dests(
+    key: str,
+    user_flat: Dict[str, Any],
+    mx: Dict[str, Tuple[torch.dtype, Tuple[int, ...]]],
+    fetches: Dict[str, Any],
+) -> List[Tuple[Tuple[torch.Tensor, torch.Tensor], torch.Tensor]]:
+    """``_plan_quant_dests`` for MXFP4 entries: an ``MxQuantizedTensor`` leaf
+    receives payload and scales in place, a tensor leaf gets scratch buffers
+    and is dequantised into afterwards.  Either must have the logical shape
+    the marker recorded."""
+    by_device: Dict[torch.device, List[str]] = {}
+    for k in user_flat:
+        if k not in mx:
+            continue
+        leaf = user_flat[k]
+        shape = tuple(mx[k][1])
+        if isinstance(leaf, MxQuantizedTensor):
+            got = (tuple(leaf.payload.shape), tuple(leaf.scales.shape))
+            if tuple(leaf.shape) != shape or got != mx_shapes(shape):
+                raise ValueError(
+                    f"MxQuantizedTensor destination for {k!r}: shape "
+                    f"{tuple(leaf.shape)} with payload/scales {got} does "
+                    f"not fit the stored entry of shape {shape}"
+                )
+            fetches[f"{key}/{k}"] = leaf.payload
+            fetches[f"{key}/{MX_SCALES_KEY}/{k}"] = leaf.scales
+        elif (
+            type(leaf) is torch.Tensor
+            and leaf.dtype in QUANT_DTYPES
+            and leaf.dim() >= 1
+        ):
+            if tuple(leaf.shape) != shape:
+                raise ValueError(
+                    f"destination for {k!r} has shape {tuple(leaf.shape)}, "
+                    f"the stored MXFP4 entry {shape}"
+                )
+            by_device.setdefault(leaf.device, []).append(k)
+        else:
+            raise TypeError(
+                f"entry {k!r} was pushed quantised: its destination must be "
+                "a plain f32/bf16/f16 tensor or an MxQuantizedTensor, got "
+                f"{type(leaf).__name__}"
+            )
+    pending = []
+    for device, ks in by_device.items():
+        bufs = alloc_mx([user_flat[k].shape for k in ks], device)
+        for k, (payload, scales) in zip(ks, bufs):
+            fetches[f"{key}/{k}"] = payload
+            fetches[f"{key}/{MX_SCALES_KEY}/{k}"] = scales
+            pending.append(((payload, scales), user_flat[k]))
+    return pending
+
+
 # per-(client, key) direct-sync endpoints, built lazily on first use
 _direct_sources: Dict[tuple, Any] = {}
 _direct_dests: Dict[tuple, Any] = {}
@@ -235,7 +337,7 @@ async def put_state_dict(
     rank: Optional[int] = None,
     world_size: Optional[int] = None,
     direct_rdma: bool = False,  # reference-compat alias for ``direct``
-    transfer_quant: Union[None, str, Fp8BlockQuant] = None,
+    transfer_quant: TransferQuant = None,
 ) -> None:
     direct = direct or direct_rdma
     quant = _resolve_quant(transfer_quant)
@@ -263,8 +365,17 @@ async def put_state_dict(
         # the whole dict in one kernel launch, before the split into
         # sub-batches; the other floating entries still take transfer_dtype
         qkeys = [k for k, v in flat.items() if quant.selects(k, v)]
-        pairs = dict(zip(qkeys, quantize_fp8([flat[k] for k in qkeys])))
-        mapping = QuantMapping(mapping, {k: flat[k].dtype for k in qkeys})
+        if isinstance(quant, Mxfp4BlockQuant):
+            scales_key = MX_SCALES_KEY
+            pairs = dict(zip(qkeys, quantize_mxfp4([flat[k] for k in qkeys])))
+            mapping = QuantMapping(
+                mapping,
+                mx={k: (flat[k].dtype, tuple(flat[k].shape)) for k in qkeys},
+            )
+        else:
+            scales_key = SCALES_KEY
+            pairs = dict(zip(qkeys, quantize_fp8([flat[k] for k in qkeys])))
+            mapping = QuantMapping(mapping, {k: flat[k].dtype for k in qkeys})
         rest = _cast_floating(
             {k: v for k, v in flat.items() if k not in pairs}, transfer_dtype
         )
@@ -273,7 +384,7 @@ async def put_state_dict(
         staged: Dict[str, Any] = {}
         for k in flat:
             if k in pairs:
-                staged[k], staged[f"{SCALES_KEY}/{k}"] = pairs[k]
+                staged[k], staged[f"{scales_key}/{k}"] = pairs[k]
             else:
                 staged[k] = rest[k]
         flat = staged
@@ -303,10 +414,11 @@ async def get_state_dict(
 ) -> Dict[str, Any]:
     """``dequantize`` matters only for entries pushed with ``transfer_quant``
     and only when no ``user_state_dict`` is given: ``False`` returns them as
-    :class:`QuantizedTensor` leaves instead of tensors of the original
-    dtype.  With a ``user_state_dict`` the destination leaf decides: a
-    tensor (f32/bf16/f16) is dequantised into, a ``QuantizedTensor`` receives
-    payload and scales as stored."""
+    :class:`QuantizedTensor` (FP8) or :class:`MxQuantizedTensor` (MXFP4)
+    leaves instead of tensors of the original dtype.  With a
+    ``user_state_dict`` the destination leaf decides: a tensor (f32/bf16/f16)
+    is dequantised into, a ``QuantizedTensor`` / ``MxQuantizedTensor``
+    receives payload and scales as stored."""
     direct = direct or direct_rdma
     if direct:
         from torchstore_amd.weight_sync import DirectWeightSyncDest
@@ -331,6 +443,10 @@ async def get_state_dict(
     # {flat_key: original dtype} of the quantised entries; empty for a
     # plain push, and then everything below is what it always was
     quant: Dict[str, torch.dtype] = getattr(mapping, "quant", {})
+    # {flat_key: (original dtype, logical shape)} of the MXFP4 entries
+    mx: Dict[str, Tuple[torch.dtype, Tuple[int, ...]]] = getattr(
+        mapping, "mx", {}
+    )
 
     if user_state_dict is not None:
         user_flat, user_mapping = _flatten(user_state_dict)
@@ -350,7 +466,8 @@ async def get_state_dict(
                 )
         fetches = {f"{key}/{k}": v for k, v in user_flat.items()}
         pending = _plan_quant_dests(key, user_flat, quant, fetches)
-        if quant:
+        mx_pending = _plan_mx_dests(key, user_flat, mx, fetches)
+        if quant or mx:
             fetches = _scales_beside_payloads(fetches, key, user_flat)
         chunks = await asyncio.gather(
             *(
@@ -363,13 +480,21 @@ async def get_state_dict(
             results.update(c)
         tracker.step("get_batch", _nbytes(user_flat))
         flat = {
-            k: user_flat[k] if k in quant else results[f"{key}/{k}"]
+            k: user_flat[k]
+            if k in quant or k in mx
+            else results[f"{key}/{k}"]
             for k in user_flat
         }
         if pending:
             # one batched dequant lands in the user's tensors in place
             dequantize_fp8_into(
                 [pair for pair, _ in pending], [dst for _, dst in pending]
+            )
+            tracker.step("dequant")
+        if mx_pending:
+            dequantize_mxfp4_into(
+                [pair for pair, _ in mx_pending],
+                [dst for _, dst in mx_pending],
             )
             tracker.step("dequant")
         out = _unflatten(flat, user_mapping)
@@ -380,6 +505,9 @@ async def get_state_dict(
     fetches = {f"{key}/{k}": None for k in flat_keys}
     if quant:
         fetches.update({f"{key}/{SCALES_KEY}/{k}": None for k in quant})
+        fetches = _scales_beside_payloads(fetches, key, flat_keys)
+    if mx:
+        fetches.update({f"{key}/{MX_SCALES_KEY}/{k}": None for k in mx})
         fetches = _scales_beside_payloads(fetches, key, flat_keys)
     chunks = await asyncio.gather(
         *(
@@ -411,6 +539,25 @@ async def get_state_dict(
             tracker.step("dequant")
         else:
             flat.update(leaves)
+    if mx:
+        mx_leaves = {
+            k: MxQuantizedTensor(
+                flat[k], results[f"{key}/{MX_SCALES_KEY}/{k}"], shape, dtype
+            )
+            for k, (dtype, shape) in mx.items()
+        }
+        if dequantize:
+            outs = [
+                torch.empty(q.shape, dtype=q.orig_dtype, device=q.payload.device)
+                for q in mx_leaves.values()
+            ]
+            dequantize_mxfp4_into(
+                [(q.payload, q.scales) for q in mx_leaves.values()], outs
+            )
+            flat.update(zip(mx_leaves.keys(), outs))
+            tracker.step("dequant")
+        else:
+            flat.update(mx_leaves)
     out = _unflatten(flat, mapping)
     tracker.e2e(_nbytes(flat))
     return out
