@@ -84,6 +84,40 @@ def test_pin_fail_open(monkeypatch):
     pinned.clear()  # avoid unregister on a fake
 
 
+def test_pin_failure_clears_hip_error(monkeypatch):
+    """A failed register leaves its code as HIP's last error, which torch's
+    next launch would raise as its own: every failure must clear it (also
+    the ones that no longer warn), a success must not."""
+    import warnings
+
+    from torchstore_amd.transport import shm
+
+    rc = {"value": 1}  # hipErrorInvalidValue
+
+    class FakeCudart:
+        def cudaHostRegister(self, ptr, nbytes, flags):
+            return rc["value"]
+
+    cleared = []
+    monkeypatch.setattr(torch.cuda, "is_available", lambda: True)
+    monkeypatch.setattr(torch.cuda, "cudart", lambda: FakeCudart())
+    monkeypatch.setattr(shm, "_PIN_WARNED", set())
+    monkeypatch.setattr(shm, "_clear_hip_error", lambda: cleared.append(1))
+
+    seg = shm._allocate_segment(4096)
+    pinned = {}
+    with warnings.catch_warnings():
+        warnings.simplefilter("ignore")
+        shm._try_pin(seg, pinned)
+        shm._try_pin(seg, pinned)
+    assert len(cleared) == 2 and pinned == {}
+
+    rc["value"] = 0
+    shm._try_pin(seg, pinned)
+    assert len(cleared) == 2 and len(pinned) == 1
+    pinned.clear()  # avoid unregister on a fake
+
+
 def test_context_strip_on_serialization():
     buf = RpcTransportBuffer()
     buf.bind_client(object(), TransportContext())

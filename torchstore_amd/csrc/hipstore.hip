@@ -29,7 +29,8 @@
 //   * quant_mx_batch / dequant_mx_batch (quant_mx.h) — K6/K7: MXFP4 (packed
 //     OCP e2m1, 32-element blocks, e8m0 scale bytes) the same way, with a
 //     launch counter of their own.
-//   * host_register / host_unregister — pin SHM pages for DMA.
+//   * host_register / host_unregister — pin SHM pages for DMA;
+//     clear_last_error — drop the code a failed pin made elsewhere left.
 // Underneath: plan.h turns the python tuples into descriptors (HIP-free; also
 // built on the CPU by tests/native/plan_check.cpp), desc_ring.h stages them
 // on the device, unit_walk.h finds a unit's descriptor inside the kernels,
@@ -213,6 +214,12 @@ static void host_unregister(uintptr_t ptr) {
   HIP_CHECK(hipHostUnregister(reinterpret_cast<void*>(ptr)));
 }
 
+// A failed HIP call made OUTSIDE this module (torch's cudart binding has no
+// hipGetLastError) leaves its code as the thread's last error, and torch's
+// next launch check would report it.  HIP keeps that per thread: call this
+// on the thread that saw the failure.
+static int clear_last_error() { return static_cast<int>(hipGetLastError()); }
+
 static int device_count() {
   int n = 0;
   hipError_t e = hipGetDeviceCount(&n);
@@ -271,6 +278,7 @@ PYBIND11_MODULE(_hipstore, m) {
         py::call_guard<py::gil_scoped_release>());
   m.def("host_register", &host_register);
   m.def("host_unregister", &host_unregister);
+  m.def("clear_last_error", &clear_last_error);
   m.def("device_count", &device_count);
   // flat-kernel defaults and launch counter, for the tests and A/B runs
   m.attr("FLAT_SPAN_DEFAULT") = kFlatSpanDefault;

@@ -106,6 +106,21 @@ def _pin_enabled() -> bool:
     return os.environ.get("TORCHSTORE_AMD_PIN_SHM", "1") != "0"
 
 
+def _clear_hip_error() -> None:
+    """Drop the error code a failed hipHostRegister leaves behind.
+
+    HIP keeps the code of a failed call as the thread's last error, and
+    torch's next kernel launch would raise it as its own — failing open has
+    to clear it.  torch's cudart binding cannot, so the extension does.
+    """
+    from torchstore_amd.ops import gpu as gpu_ops
+
+    try:
+        gpu_ops.ext().clear_last_error()
+    except RuntimeError:
+        pass  # eager fallback without the extension: no way to reach HIP
+
+
 def _try_pin(seg_u8: torch.Tensor, pinned: Dict[int, int]) -> None:
     """Pin a segment's pages for DMA; fail-open (copies still work unpinned)."""
     if not torch.cuda.is_available() or not _pin_enabled():
@@ -124,7 +139,9 @@ def _try_pin(seg_u8: torch.Tensor, pinned: Dict[int, int]) -> None:
         rc = exc
     if code == 0:
         pinned[ptr] = nbytes
-    elif code not in _PIN_WARNED:
+        return
+    _clear_hip_error()
+    if code not in _PIN_WARNED:
         _PIN_WARNED.add(code)
         warnings.warn(
             f"hipHostRegister failed (code {rc}); shared-memory GPU copies "
