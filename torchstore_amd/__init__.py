@@ -33,9 +33,14 @@ from torchstore_amd.api import (
     stats,
 )
 from torchstore_amd.ops.mx import MxQuantizedTensor
+from torchstore_amd.ops.mx6 import Mxfp6QuantizedTensor
 from torchstore_amd.ops.quant import QuantizedTensor
 from torchstore_amd.spmd import SPMDEnv, initialize_spmd, shutdown_spmd
-from torchstore_amd.state_dict import Fp8BlockQuant, Mxfp4BlockQuant
+from torchstore_amd.state_dict import (
+    Fp8BlockQuant,
+    Mxfp4BlockQuant,
+    Mxfp6BlockQuant,
+)
 from torchstore_amd.strategy import (
     HostStrategy,
     LocalRankStrategy,
@@ -78,7 +83,9 @@ __all__ = [
     "TransportType",
     "Fp8BlockQuant",
     "Mxfp4BlockQuant",
+    "Mxfp6BlockQuant",
     "MxQuantizedTensor",
+    "Mxfp6QuantizedTensor",
     "QuantizedTensor",
     "LocalShard",
     "Request",

@@ -44,6 +44,7 @@
 //                                                16-element kernel
 //   HIPSTORE_QUANT_GRID   65536                  >= 64
 //   HIPSTORE_MX_GRID      65536                  >= 64
+//   HIPSTORE_MX6_GRID     65536                  >= 64
 //
 // The measurements behind each default stand next to the code that uses it.
 

@@ -29,6 +29,9 @@
 //   * quant_mx_batch / dequant_mx_batch (quant_mx.h) — K6/K7: MXFP4 (packed
 //     OCP e2m1, 32-element blocks, e8m0 scale bytes) the same way, with a
 //     launch counter of their own.
+//   * quant_mx6_batch / dequant_mx6_batch (quant_mx6.h) — K8/K9: MXFP6
+//     (packed OCP e2m3, 6 bits per element, the same blocks and scales), again
+//     with a launch counter of their own.
 //   * host_register / host_unregister — pin SHM pages for DMA;
 //     clear_last_error — drop the code a failed pin made elsewhere left.
 // Underneath: plan.h turns the python tuples into descriptors (HIP-free; also
@@ -49,6 +52,7 @@
 #include "plan.h"
 #include "quant_fp8.h"
 #include "quant_mx.h"
+#include "quant_mx6.h"
 
 #include <pybind11/pybind11.h>
 #include <pybind11/stl.h>
@@ -189,6 +193,20 @@ static void quant_mx_batch(const std::vector<PyQuantItem>& items, int device,
                            reinterpret_cast<hipStream_t>(stream_handle));
 }
 
+// K8/K9; the same tuples and plan, the payload being 6 bits per element
+template <bool DEQUANT>
+static void quant_mx6_batch(const std::vector<PyQuantItem>& items, int device,
+                            uintptr_t stream_handle) {
+  std::vector<QuantIn> in;
+  in.reserve(items.size());
+  for (const auto& it : items) {
+    const auto& [wide, payload, scales, rows, cols, dtype] = it;
+    in.push_back(QuantIn{wide, payload, scales, rows, cols, dtype});
+  }
+  launch_quant_mx6<DEQUANT>(plan_mx(in), device,
+                            reinterpret_cast<hipStream_t>(stream_handle));
+}
+
 // host pinning and staging
 
 // single UVA-resolved copy on a dedicated pool stream (blocking).  Used by
@@ -273,6 +291,16 @@ PYBIND11_MODULE(_hipstore, m) {
   });
   m.attr("MX_BLOCK") = kMxBlock;
   m.attr("MX_LANES") = kMxLanes;
+  m.def("quant_mx6_batch", &quant_mx6_batch<false>, py::arg("items"),
+        py::arg("device"), py::arg("stream"),
+        py::call_guard<py::gil_scoped_release>());
+  m.def("dequant_mx6_batch", &quant_mx6_batch<true>, py::arg("items"),
+        py::arg("device"), py::arg("stream"),
+        py::call_guard<py::gil_scoped_release>());
+  m.def("mx6_launches", []() {
+    return g_mx6_launches.load(std::memory_order_relaxed);
+  });
+  m.attr("MX6_LDS") = kMx6Lds;
   m.def("sdma_copy", &sdma_copy, py::arg("dst"), py::arg("src"),
         py::arg("nbytes"), py::arg("device"),
         py::call_guard<py::gil_scoped_release>());

@@ -27,6 +27,13 @@ static constexpr uint32_t kQuantUnitBlocks = 32 * kQuantPasses;
 static constexpr uint32_t kMxBlock = 32;
 static constexpr uint32_t kMxUnitBlocks = 256;
 
+// MXFP6 (e2m3): the same blocks, units, descriptor (MxDesc) and planner
+// (plan_mx, whose fast rule "both bases 16B aligned, whole blocks only" is
+// also what quant_mx6.h needs); only the payload differs, 6 bits per element:
+// a full block is 24 bytes, a row ceil(3 cols / 4), and the kernels derive
+// both from `cols`
+static constexpr uint32_t kMx6BlockBytes = kMxBlock * 6 / 8;
+
 // descriptors (read by the kernels; every one carries the exclusive prefix
 // sum of units that unit_walk.h searches)
 
@@ -76,10 +83,12 @@ struct QuantDesc {
 };
 static_assert(sizeof(QuantDesc) == 64, "QuantDesc is meant to be 64 bytes");
 
-// K6/K7: unit = kMxUnitBlocks consecutive 32-element blocks of a tensor
+// K6/K7 and K8/K9: unit = kMxUnitBlocks consecutive 32-element blocks of a
+// tensor
 struct MxDesc {
   uintptr_t wide;         // f32/bf16/f16 tensor: quant source, dequant dest
   uintptr_t payload;      // packed e2m1, rows of ceil(cols / 2) bytes
+                          // (MXFP6: packed e2m3, rows of ceil(3 cols / 4))
   uintptr_t scales;       // e8m0 bytes [rows, nblk]
   uint64_t rows;
   uint64_t units_prefix;  // exclusive prefix sum of units

@@ -6,6 +6,7 @@ The extension is built in-tree for gfx950 (``python setup.py build_ext
 * K1 slice-gather / K2 batched multi-slice-scatter / K3 fused cast kernels;
 * K4/K5 batched block-scaled FP8 quantise / dequantise kernels;
 * K6/K7 batched MXFP4 (packed e2m1 + e8m0 block scales) kernels;
+* K8/K9 batched MXFP6 (packed e2m3, the same scales) kernels;
 * HIP IPC: export/open ``hipIpcMemHandle_t``, batched peer copies on
   dedicated streams, event completion;
 * host page pinning (``hipHostRegister``) for the SHM transport.
@@ -160,6 +161,29 @@ def dequant_mx_batch(triples, device: torch.device) -> None:
 def mx_launches() -> int:
     """Launches of K6 + K7 so far (counted apart from K4/K5)."""
     return ext().mx_launches()
+
+
+def quant_mx6_batch(triples, device: torch.device) -> None:
+    """K8: ``[(src, payload, scales), ...]`` — MXFP6 quantise of N tensors
+    in ONE launch on the caller's current stream (async).  ``payload`` and
+    ``scales`` are the uint8 buffers of ``ops.mx6.mx6_shapes(src.shape)``."""
+    ext().quant_mx6_batch(
+        _quant_items(triples, "mxfp6"), device.index, _stream(device)
+    )
+
+
+def dequant_mx6_batch(triples, device: torch.device) -> None:
+    """K9: ``[(dst, payload, scales), ...]`` — the mirror image of K8; the
+    destination's shape is the logical one and its dtype (f32/bf16/f16)
+    decides the output rounding."""
+    ext().dequant_mx6_batch(
+        _quant_items(triples, "mxfp6"), device.index, _stream(device)
+    )
+
+
+def mx6_launches() -> int:
+    """Launches of K8 + K9 so far (counted apart from K4/K5 and K6/K7)."""
+    return ext().mx6_launches()
 
 
 # a contiguous source below this many bytes is ONE flat descriptor; the

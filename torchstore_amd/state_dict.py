@@ -22,7 +22,10 @@ original dtype, so readers learn it from the fetch they already make.
 ``transfer_quant="mxfp4"`` does the same with MXFP4 (``ops/mx.py``): scales
 under ``"{key}/<MX_SCALES>/{flat_key}"``, and the marker's ``mx`` field
 records the original dtype and the logical shape (an odd last dimension
-cannot be told from the packed payload).  A push uses one policy.
+cannot be told from the packed payload).  ``transfer_quant="mxfp6_e2m3"`` is
+MXFP6 (``ops/mx6.py``) in the same way: scales under
+``"{key}/<MX6_SCALES>/{flat_key}"``, marker field ``mx6``.  A push uses one
+policy.
 """
 
 from __future__ import annotations
@@ -31,7 +34,7 @@ import asyncio
 import fnmatch
 import os
 from dataclasses import dataclass
-from typing import Any, Dict, List, Optional, Sequence, Tuple, Union
+from typing import Any, Callable, Dict, List, Optional, Sequence, Tuple, Union
 
 import torch
 
@@ -42,6 +45,13 @@ from torchstore_amd.ops.mx import (
     dequantize_mxfp4_into,
     mx_shapes,
     quantize_mxfp4,
+)
+from torchstore_amd.ops.mx6 import (
+    Mxfp6QuantizedTensor,
+    alloc_mx6,
+    dequantize_mxfp6_into,
+    mx6_shapes,
+    quantize_mxfp6,
 )
 from torchstore_amd.ops.quant import (
     QUANT_DTYPES,
@@ -60,7 +70,8 @@ MAPPING_KEY = "<MAPPING>"
 # <MAPPING>: a flat key never starts with an angle-bracket segment of ours
 SCALES_KEY = "<FP8_SCALES>"
 MX_SCALES_KEY = "<MX_SCALES>"
-_SCALES_KEYS = (SCALES_KEY, MX_SCALES_KEY)
+MX6_SCALES_KEY = "<MX6_SCALES>"
+_SCALES_KEYS = (SCALES_KEY, MX_SCALES_KEY, MX6_SCALES_KEY)
 
 
 def _selects(policy, flat_key: str, value: Any) -> bool:
@@ -103,46 +114,90 @@ class Mxfp4BlockQuant:
         return _selects(self, flat_key, value)
 
 
-TransferQuant = Union[None, str, Fp8BlockQuant, Mxfp4BlockQuant]
+@dataclass(frozen=True)
+class Mxfp6BlockQuant:
+    """``transfer_quant`` policy: MXFP6, packed e2m3 values with one e8m0
+    scale byte per block of 32 (``ops/mx6.py``).  Selects entries by the same
+    rule as :class:`Fp8BlockQuant`."""
+
+    min_numel: int = 0
+    exclude: Sequence[str] = ()
+
+    def selects(self, flat_key: str, value: Any) -> bool:
+        return _selects(self, flat_key, value)
+
+
+_POLICIES = (Fp8BlockQuant, Mxfp4BlockQuant, Mxfp6BlockQuant)
+TransferQuant = Union[None, str, Fp8BlockQuant, Mxfp4BlockQuant, Mxfp6BlockQuant]
 
 
 def _resolve_quant(
     transfer_quant: TransferQuant,
-) -> Union[None, Fp8BlockQuant, Mxfp4BlockQuant]:
-    if transfer_quant is None or isinstance(
-        transfer_quant, (Fp8BlockQuant, Mxfp4BlockQuant)
-    ):
+) -> Union[None, Fp8BlockQuant, Mxfp4BlockQuant, Mxfp6BlockQuant]:
+    if transfer_quant is None or isinstance(transfer_quant, _POLICIES):
         return transfer_quant
     if transfer_quant == "fp8_e4m3":
         return Fp8BlockQuant()
     if transfer_quant == "mxfp4":
         return Mxfp4BlockQuant()
+    if transfer_quant == "mxfp6_e2m3":
+        return Mxfp6BlockQuant()
     raise ValueError(
         f"unknown transfer_quant {transfer_quant!r}: expected 'fp8_e4m3', "
-        "'mxfp4', an Fp8BlockQuant or an Mxfp4BlockQuant"
+        "'mxfp4', 'mxfp6_e2m3', an Fp8BlockQuant, an Mxfp4BlockQuant or an "
+        "Mxfp6BlockQuant"
     )
+
+
+@dataclass(frozen=True)
+class _MxFormat:
+    """Where the two microscaling formats differ on this side of the store."""
+
+    name: str  # as messages spell it
+    field: str  # the QuantMapping attribute that lists its entries
+    scales_key: str
+    leaf: type  # the class of a quantised leaf
+    shapes: Callable  # logical shape -> (payload shape, scales shape)
+    alloc: Callable
+    quantize: Callable
+    dequantize_into: Callable
+
+
+_MXFP4 = _MxFormat(
+    "MXFP4", "mx", MX_SCALES_KEY, MxQuantizedTensor, mx_shapes, alloc_mx,
+    quantize_mxfp4, dequantize_mxfp4_into,
+)
+_MXFP6 = _MxFormat(
+    "MXFP6", "mx6", MX6_SCALES_KEY, Mxfp6QuantizedTensor, mx6_shapes,
+    alloc_mx6, quantize_mxfp6, dequantize_mxfp6_into,
+)
 
 
 class QuantMapping(dict):
     """The commit marker of a quantised push: the usual flat-key mapping plus
-    ``quant``, ``{flat_key: original dtype}`` of the FP8 entries, or ``mx``,
-    ``{flat_key: (original dtype, logical shape)}`` of the MXFP4 ones.  A
-    plain push keeps writing a plain dict, so readers tell them apart from
-    the marker they fetch anyway."""
+    ``quant``, ``{flat_key: original dtype}`` of the FP8 entries, or ``mx``
+    / ``mx6``, ``{flat_key: (original dtype, logical shape)}`` of the MXFP4 /
+    MXFP6 ones.  A plain push keeps writing a plain dict, so readers tell
+    them apart from the marker they fetch anyway."""
 
     def __init__(
         self,
         mapping=(),
         quant: Optional[Dict[str, torch.dtype]] = None,
         mx: Optional[Dict[str, Tuple[torch.dtype, Tuple[int, ...]]]] = None,
+        mx6: Optional[Dict[str, Tuple[torch.dtype, Tuple[int, ...]]]] = None,
     ):
         super().__init__(mapping)
         self.quant = dict(quant or {})
         self.mx = dict(mx or {})
+        self.mx6 = dict(mx6 or {})
 
     def __reduce__(self):
-        # without MXFP4 entries the marker pickles as it did before they
-        # existed: plain and FP8 pushes stay byte-identical on the wire
+        # a field is emitted only from the first format that needs it on, so
+        # the marker of a plain, FP8 or MXFP4 push pickles as it did before
+        # the later formats existed: byte-identical on the wire
+        if self.mx6:
+            return (QuantMapping, (dict(self), self.quant, self.mx, self.mx6))
         if not self.mx:
             return (QuantMapping, (dict(self), self.quant))
         return (QuantMapping, (dict(self), self.quant, self.mx))
@@ -275,27 +330,28 @@ def _plan_mx_dests(
     user_flat: Dict[str, Any],
     mx: Dict[str, Tuple[torch.dtype, Tuple[int, ...]]],
     fetches: Dict[str, Any],
+    fmt: _MxFormat = _MXFP4,
 ) -> List[Tuple[Tuple[torch.Tensor, torch.Tensor], torch.Tensor]]:
-    """``_plan_quant_dests`` for MXFP4 entries: an ``MxQuantizedTensor`` leaf
-    receives payload and scales in place, a tensor leaf gets scratch buffers
-    and is dequantised into afterwards.  Either must have the logical shape
-    the marker recorded."""
+    """``_plan_quant_dests`` for the MXFP4 or MXFP6 entries ``mx``: a leaf of
+    the format's own class receives payload and scales in place, a tensor
+    leaf gets scratch buffers and is dequantised into afterwards.  Either
+    must have the logical shape the marker recorded."""
     by_device: Dict[torch.device, List[str]] = {}
     for k in user_flat:
         if k not in mx:
             continue
         leaf = user_flat[k]
         shape = tuple(mx[k][1])
-        if isinstance(leaf, MxQuantizedTensor):
+        if isinstance(leaf, fmt.leaf):
             got = (tuple(leaf.payload.shape), tuple(leaf.scales.shape))
-            if tuple(leaf.shape) != shape or got != mx_shapes(shape):
+            if tuple(leaf.shape) != shape or got != fmt.shapes(shape):
                 raise ValueError(
-                    f"MxQuantizedTensor destination for {k!r}: shape "
+                    f"{fmt.leaf.__name__} destination for {k!r}: shape "
                     f"{tuple(leaf.shape)} with payload/scales {got} does "
                     f"not fit the stored entry of shape {shape}"
                 )
             fetches[f"{key}/{k}"] = leaf.payload
-            fetches[f"{key}/{MX_SCALES_KEY}/{k}"] = leaf.scales
+            fetches[f"{key}/{fmt.scales_key}/{k}"] = leaf.scales
         elif (
             type(leaf) is torch.Tensor
             and leaf.dtype in QUANT_DTYPES
@@ -304,21 +360,21 @@ def _plan_mx_dests(
             if tuple(leaf.shape) != shape:
                 raise ValueError(
                     f"destination for {k!r} has shape {tuple(leaf.shape)}, "
-                    f"the stored MXFP4 entry {shape}"
+                    f"the stored {fmt.name} entry {shape}"
                 )
             by_device.setdefault(leaf.device, []).append(k)
         else:
             raise TypeError(
                 f"entry {k!r} was pushed quantised: its destination must be "
-                "a plain f32/bf16/f16 tensor or an MxQuantizedTensor, got "
+                f"a plain f32/bf16/f16 tensor or an {fmt.leaf.__name__}, got "
                 f"{type(leaf).__name__}"
             )
     pending = []
     for device, ks in by_device.items():
-        bufs = alloc_mx([user_flat[k].shape for k in ks], device)
+        bufs = fmt.alloc([user_flat[k].shape for k in ks], device)
         for k, (payload, scales) in zip(ks, bufs):
             fetches[f"{key}/{k}"] = payload
-            fetches[f"{key}/{MX_SCALES_KEY}/{k}"] = scales
+            fetches[f"{key}/{fmt.scales_key}/{k}"] = scales
             pending.append(((payload, scales), user_flat[k]))
     return pending
 
@@ -365,13 +421,12 @@ async def put_state_dict(
         # the whole dict in one kernel launch, before the split into
         # sub-batches; the other floating entries still take transfer_dtype
         qkeys = [k for k, v in flat.items() if quant.selects(k, v)]
-        if isinstance(quant, Mxfp4BlockQuant):
-            scales_key = MX_SCALES_KEY
-            pairs = dict(zip(qkeys, quantize_mxfp4([flat[k] for k in qkeys])))
-            mapping = QuantMapping(
-                mapping,
-                mx={k: (flat[k].dtype, tuple(flat[k].shape)) for k in qkeys},
-            )
+        if isinstance(quant, (Mxfp4BlockQuant, Mxfp6BlockQuant)):
+            fmt = _MXFP4 if isinstance(quant, Mxfp4BlockQuant) else _MXFP6
+            scales_key = fmt.scales_key
+            pairs = dict(zip(qkeys, fmt.quantize([flat[k] for k in qkeys])))
+            entries = {k: (flat[k].dtype, tuple(flat[k].shape)) for k in qkeys}
+            mapping = QuantMapping(mapping, **{fmt.field: entries})
         else:
             scales_key = SCALES_KEY
             pairs = dict(zip(qkeys, quantize_fp8([flat[k] for k in qkeys])))
@@ -414,11 +469,12 @@ async def get_state_dict(
 ) -> Dict[str, Any]:
     """``dequantize`` matters only for entries pushed with ``transfer_quant``
     and only when no ``user_state_dict`` is given: ``False`` returns them as
-    :class:`QuantizedTensor` (FP8) or :class:`MxQuantizedTensor` (MXFP4)
-    leaves instead of tensors of the original dtype.  With a
-    ``user_state_dict`` the destination leaf decides: a tensor (f32/bf16/f16)
-    is dequantised into, a ``QuantizedTensor`` / ``MxQuantizedTensor``
-    receives payload and scales as stored."""
+    :class:`QuantizedTensor` (FP8), :class:`MxQuantizedTensor` (MXFP4) or
+    :class:`Mxfp6QuantizedTensor` (MXFP6) leaves instead of tensors of the
+    original dtype.  With a ``user_state_dict`` the destination leaf decides:
+    a tensor (f32/bf16/f16) is dequantised into, a ``QuantizedTensor`` /
+    ``MxQuantizedTensor`` / ``Mxfp6QuantizedTensor`` receives payload and
+    scales as stored."""
     direct = direct or direct_rdma
     if direct:
         from torchstore_amd.weight_sync import DirectWeightSyncDest
@@ -443,9 +499,11 @@ async def get_state_dict(
     # {flat_key: original dtype} of the quantised entries; empty for a
     # plain push, and then everything below is what it always was
     quant: Dict[str, torch.dtype] = getattr(mapping, "quant", {})
-    # {flat_key: (original dtype, logical shape)} of the MXFP4 entries
+    # {flat_key: (original dtype, logical shape)} of the MXFP4 or MXFP6
+    # entries, with their format (a push uses one)
+    mx_fmt = _MXFP6 if getattr(mapping, "mx6", None) else _MXFP4
     mx: Dict[str, Tuple[torch.dtype, Tuple[int, ...]]] = getattr(
-        mapping, "mx", {}
+        mapping, mx_fmt.field, {}
     )
 
     if user_state_dict is not None:
@@ -466,7 +524,7 @@ async def get_state_dict(
                 )
         fetches = {f"{key}/{k}": v for k, v in user_flat.items()}
         pending = _plan_quant_dests(key, user_flat, quant, fetches)
-        mx_pending = _plan_mx_dests(key, user_flat, mx, fetches)
+        mx_pending = _plan_mx_dests(key, user_flat, mx, fetches, mx_fmt)
         if quant or mx:
             fetches = _scales_beside_payloads(fetches, key, user_flat)
         chunks = await asyncio.gather(
@@ -492,7 +550,7 @@ async def get_state_dict(
             )
             tracker.step("dequant")
         if mx_pending:
-            dequantize_mxfp4_into(
+            mx_fmt.dequantize_into(
                 [pair for pair, _ in mx_pending],
                 [dst for _, dst in mx_pending],
             )
@@ -507,7 +565,7 @@ async def get_state_dict(
         fetches.update({f"{key}/{SCALES_KEY}/{k}": None for k in quant})
         fetches = _scales_beside_payloads(fetches, key, flat_keys)
     if mx:
-        fetches.update({f"{key}/{MX_SCALES_KEY}/{k}": None for k in mx})
+        fetches.update({f"{key}/{mx_fmt.scales_key}/{k}": None for k in mx})
         fetches = _scales_beside_payloads(fetches, key, flat_keys)
     chunks = await asyncio.gather(
         *(
@@ -541,8 +599,8 @@ async def get_state_dict(
             flat.update(leaves)
     if mx:
         mx_leaves = {
-            k: MxQuantizedTensor(
-                flat[k], results[f"{key}/{MX_SCALES_KEY}/{k}"], shape, dtype
+            k: mx_fmt.leaf(
+                flat[k], results[f"{key}/{mx_fmt.scales_key}/{k}"], shape, dtype
             )
             for k, (dtype, shape) in mx.items()
         }
@@ -551,7 +609,7 @@ async def get_state_dict(
                 torch.empty(q.shape, dtype=q.orig_dtype, device=q.payload.device)
                 for q in mx_leaves.values()
             ]
-            dequantize_mxfp4_into(
+            mx_fmt.dequantize_into(
                 [(q.payload, q.scales) for q in mx_leaves.values()], outs
             )
             flat.update(zip(mx_leaves.keys(), outs))
