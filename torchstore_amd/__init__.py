@@ -35,9 +35,11 @@ from torchstore_amd.api import (
 from torchstore_amd.ops.mx import MxQuantizedTensor
 from torchstore_amd.ops.mx6 import Mxfp6QuantizedTensor
 from torchstore_amd.ops.quant import QuantizedTensor
+from torchstore_amd.ops.quant_row import RowQuantizedTensor
 from torchstore_amd.spmd import SPMDEnv, initialize_spmd, shutdown_spmd
 from torchstore_amd.state_dict import (
     Fp8BlockQuant,
+    Fp8RowQuant,
     Mxfp4BlockQuant,
     Mxfp6BlockQuant,
 )
@@ -82,11 +84,13 @@ __all__ = [
     "SingletonStrategy",
     "TransportType",
     "Fp8BlockQuant",
+    "Fp8RowQuant",
     "Mxfp4BlockQuant",
     "Mxfp6BlockQuant",
     "MxQuantizedTensor",
     "Mxfp6QuantizedTensor",
     "QuantizedTensor",
+    "RowQuantizedTensor",
     "LocalShard",
     "Request",
     "TensorSlice",

@@ -45,6 +45,11 @@
 //   HIPSTORE_QUANT_GRID   65536                  >= 64
 //   HIPSTORE_MX_GRID      65536                  >= 64
 //   HIPSTORE_MX6_GRID     65536                  >= 64
+//   HIPSTORE_ROW_GRID     65536                  >= 64
+//   HIPSTORE_ROW_WAVE     4096                   <= 4096: longest row a wave
+//                                                takes (row-scaled FP8)
+//   HIPSTORE_ROW_WG       16384                  <= 16384: longest row a
+//                                                workgroup holds in registers
 //
 // The measurements behind each default stand next to the code that uses it.
 

@@ -32,6 +32,9 @@
 //   * quant_mx6_batch / dequant_mx6_batch (quant_mx6.h) — K8/K9: MXFP6
 //     (packed OCP e2m3, 6 bits per element, the same blocks and scales), again
 //     with a launch counter of their own.
+//   * quant_row_batch / dequant_row_batch (quant_row.h) — K10/K11: row-scaled
+//     FP8 (e4m3, one f32 scale per row: the operand of row-wise scaled GEMMs),
+//     a wave, a workgroup in registers or a workgroup streaming per row.
 //   * host_register / host_unregister — pin SHM pages for DMA;
 //     clear_last_error — drop the code a failed pin made elsewhere left.
 // Underneath: plan.h turns the python tuples into descriptors (HIP-free; also
@@ -53,6 +56,7 @@
 #include "quant_fp8.h"
 #include "quant_mx.h"
 #include "quant_mx6.h"
+#include "quant_row.h"
 
 #include <pybind11/pybind11.h>
 #include <pybind11/stl.h>
@@ -207,6 +211,27 @@ static void quant_mx6_batch(const std::vector<PyQuantItem>& items, int device,
                             reinterpret_cast<hipStream_t>(stream_handle));
 }
 
+// K10/K11; the same tuples, scales being one f32 per row.  The regime limits
+// default to what the kernels can hold (row_limits) and can only be lowered
+template <bool DEQUANT>
+static void quant_row_batch(const std::vector<PyQuantItem>& items, int device,
+                            uintptr_t stream_handle) {
+  std::vector<QuantIn> in;
+  in.reserve(items.size());
+  for (const auto& it : items) {
+    const auto& [wide, payload, scales, rows, cols, dtype] = it;
+    in.push_back(QuantIn{wide, payload, scales, rows, cols, dtype});
+  }
+  const uint32_t wave = env_u32("HIPSTORE_ROW_WAVE", 16, kRowWave, kRowWave);
+  const uint32_t wg = env_u32("HIPSTORE_ROW_WG", 16, kRowWg, kRowWg);
+  launch_quant_row<DEQUANT>(plan_row(in, DEQUANT, wave, wg), device,
+                            reinterpret_cast<hipStream_t>(stream_handle));
+}
+
+static std::pair<uint32_t, uint32_t> row_limits() {
+  return {kRowWave, kRowWg};
+}
+
 // host pinning and staging
 
 // single UVA-resolved copy on a dedicated pool stream (blocking).  Used by
@@ -301,6 +326,16 @@ PYBIND11_MODULE(_hipstore, m) {
     return g_mx6_launches.load(std::memory_order_relaxed);
   });
   m.attr("MX6_LDS") = kMx6Lds;
+  m.def("quant_row_batch", &quant_row_batch<false>, py::arg("items"),
+        py::arg("device"), py::arg("stream"),
+        py::call_guard<py::gil_scoped_release>());
+  m.def("dequant_row_batch", &quant_row_batch<true>, py::arg("items"),
+        py::arg("device"), py::arg("stream"),
+        py::call_guard<py::gil_scoped_release>());
+  m.def("row_launches", []() {
+    return g_row_launches.load(std::memory_order_relaxed);
+  });
+  m.def("row_limits", &row_limits);
   m.def("sdma_copy", &sdma_copy, py::arg("dst"), py::arg("src"),
         py::arg("nbytes"), py::arg("device"),
         py::call_guard<py::gil_scoped_release>());

@@ -34,6 +34,22 @@ static constexpr uint32_t kMxUnitBlocks = 256;
 // both from `cols`
 static constexpr uint32_t kMx6BlockBytes = kMxBlock * 6 / 8;
 
+// Row-scaled FP8 (K10/K11): one f32 scale per row, so the quantise side
+// reduces over a whole row and picks its work split per tensor from `cols`:
+//   cols <= kRowWave            a wave holds the row in registers
+//   kRowWave < cols <= kRowWg   the workgroup holds the row in registers
+//   cols > kRowWg               the workgroup streams the row twice
+// Both limits are the register capacity of the kernels (kRowSteps 16-element
+// steps per lane) and the defaults of the planner; quant_row.h tells how they
+// were settled.
+static constexpr uint32_t kRowSteps = 4;
+static constexpr uint32_t kRowWave = kRowSteps * 64u * 16u;   // 4096
+static constexpr uint32_t kRowWg = kRowSteps * 256u * 16u;    // 16384
+static constexpr uint32_t kRowWaveRows = 4;   // rows per unit, one per wave
+// dequantise is flat: a unit is kRowDqPasses passes of 256 lanes x 16 elements
+static constexpr uint32_t kRowDqPasses = 2;
+static constexpr uint32_t kRowDqUnitElems = kRowDqPasses * 256u * 16u;
+
 // descriptors (read by the kernels; every one carries the exclusive prefix
 // sum of units that unit_walk.h searches)
 
@@ -100,6 +116,23 @@ struct MxDesc {
   uint32_t pad_;
 };
 static_assert(sizeof(MxDesc) == 64, "MxDesc is meant to be 64 bytes");
+
+// K10/K11: quantise unit = kRowWaveRows rows (mode 0) or one row (modes 1,
+// 2); dequantise unit = kRowDqUnitElems consecutive elements
+enum RowMode : uint32_t { kRowModeWave = 0, kRowModeHeld = 1, kRowModeStream = 2 };
+struct RowDesc {
+  uintptr_t wide;         // f32/bf16/f16 tensor: quant source, dequant dest
+  uintptr_t payload;      // e4m3 bytes, same element order as `wide`
+  uintptr_t scales;       // f32 [rows]
+  uint64_t rows;
+  uint64_t units_prefix;  // exclusive prefix sum of units
+  uint64_t numel;         // rows * cols
+  uint32_t cols;
+  uint32_t dtype;         // DType code of `wide` (0 = f32, 1 = f16, 2 = bf16)
+  uint32_t mode;          // RowMode of the quantise side
+  uint32_t fast;          // 1 = 16B-vector path
+};
+static_assert(sizeof(RowDesc) == 64, "RowDesc is meant to be 64 bytes");
 
 template <typename Desc>
 struct Plan {
@@ -252,6 +285,44 @@ inline Plan<MxDesc> plan_mx(const std::vector<QuantIn>& in) {
                              (uint32_t)it.cols, (uint32_t)nblk,
                              (uint32_t)nblocks, (uint32_t)it.dtype, fast, 0});
     p.units += (nblocks + kMxUnitBlocks - 1) / kMxUnitBlocks;
+  }
+  return p;
+}
+
+// Row-scaled FP8 quant / dequant plan, from the same tuples (scales: one f32
+// per row); tensors with no elements are dropped.  `wave` and `wg` are the
+// regime limits (at most kRowWave / kRowWg, what the kernels can hold).  The
+// mode and the unit count are fixed here, once per tensor, so a descriptor
+// means the same to every lane of a workgroup.
+inline Plan<RowDesc> plan_row(const std::vector<QuantIn>& in, bool dequant,
+                              uint32_t wave = kRowWave,
+                              uint32_t wg = kRowWg) {
+  if (wave > kRowWave || wg > kRowWg)
+    throw std::runtime_error("row regime limit above the kernels' capacity");
+  Plan<RowDesc> p;
+  p.descs.reserve(in.size());
+  for (const QuantIn& it : in) {
+    if (it.dtype < 0 || it.dtype > 2)
+      throw std::runtime_error("unsupported dtype");
+    if (it.rows == 0 || it.cols == 0) continue;
+    if (it.cols > UINT32_MAX)
+      throw std::runtime_error("tensor too large for one row descriptor");
+    if (it.scales & 3u) throw std::runtime_error("scales must be 4B aligned");
+    const uint32_t es = it.dtype == 0 ? 4u : 2u;
+    if (it.wide % es) throw std::runtime_error("misaligned tensor");
+    const uint32_t fast =
+        (((it.wide | it.payload) & 15u) == 0 && (it.cols & 15u) == 0) ? 1u : 0u;
+    const uint32_t mode = it.cols <= wave ? kRowModeWave
+                          : it.cols <= wg ? kRowModeHeld
+                                          : kRowModeStream;
+    const uint64_t numel = it.rows * it.cols;
+    p.descs.push_back(RowDesc{it.wide, it.payload, it.scales, it.rows, p.units,
+                              numel, (uint32_t)it.cols, (uint32_t)it.dtype,
+                              mode, fast});
+    if (dequant) p.units += (numel + kRowDqUnitElems - 1) / kRowDqUnitElems;
+    else if (mode == kRowModeWave)
+      p.units += (it.rows + kRowWaveRows - 1) / kRowWaveRows;
+    else p.units += it.rows;
   }
   return p;
 }

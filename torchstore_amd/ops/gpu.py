@@ -7,6 +7,7 @@ The extension is built in-tree for gfx950 (``python setup.py build_ext
 * K4/K5 batched block-scaled FP8 quantise / dequantise kernels;
 * K6/K7 batched MXFP4 (packed e2m1 + e8m0 block scales) kernels;
 * K8/K9 batched MXFP6 (packed e2m3, the same scales) kernels;
+* K10/K11 batched row-scaled FP8 (one f32 scale per row) kernels;
 * HIP IPC: export/open ``hipIpcMemHandle_t``, batched peer copies on
   dedicated streams, event completion;
 * host page pinning (``hipHostRegister``) for the SHM transport.
@@ -184,6 +185,35 @@ def dequant_mx6_batch(triples, device: torch.device) -> None:
 def mx6_launches() -> int:
     """Launches of K8 + K9 so far (counted apart from K4/K5 and K6/K7)."""
     return ext().mx6_launches()
+
+
+def quant_row_batch(triples, device: torch.device) -> None:
+    """K10: ``[(src, payload, scales), ...]`` — row-scaled FP8 quantise of N
+    tensors in ONE launch on the caller's current stream (async).  ``scales``
+    is the f32 buffer of ``ops.quant_row.row_scales_shape(src.shape)``."""
+    ext().quant_row_batch(
+        _quant_items(triples, "fp8 row"), device.index, _stream(device)
+    )
+
+
+def dequant_row_batch(triples, device: torch.device) -> None:
+    """K11: ``[(dst, payload, scales), ...]`` — the mirror image of K10; the
+    destination dtype (f32/bf16/f16) decides the output rounding."""
+    ext().dequant_row_batch(
+        _quant_items(triples, "fp8 row"), device.index, _stream(device)
+    )
+
+
+def row_launches() -> int:
+    """Launches of K10 + K11 so far (counted apart from the other formats)."""
+    return ext().row_launches()
+
+
+def row_limits():
+    """``(W, R)`` as compiled: a row of up to ``W`` elements is one wave's
+    work in K10, one of up to ``R`` stays in a workgroup's registers, and a
+    longer one is streamed twice."""
+    return tuple(ext().row_limits())
 
 
 # a contiguous source below this many bytes is ONE flat descriptor; the

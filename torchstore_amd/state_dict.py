@@ -24,8 +24,11 @@ under ``"{key}/<MX_SCALES>/{flat_key}"``, and the marker's ``mx`` field
 records the original dtype and the logical shape (an odd last dimension
 cannot be told from the packed payload).  ``transfer_quant="mxfp6_e2m3"`` is
 MXFP6 (``ops/mx6.py``) in the same way: scales under
-``"{key}/<MX6_SCALES>/{flat_key}"``, marker field ``mx6``.  A push uses one
-policy.
+``"{key}/<MX6_SCALES>/{flat_key}"``, marker field ``mx6``.
+``transfer_quant="fp8_e4m3_row"`` is FP8 with one scale per row
+(``ops/quant_row.py``): scales of shape ``[rows, 1]`` under
+``"{key}/<FP8_ROW_SCALES>/{flat_key}"``, marker field ``row``.  A push uses
+one policy.
 """
 
 from __future__ import annotations
@@ -61,6 +64,13 @@ from torchstore_amd.ops.quant import (
     quantize_fp8,
     scales_shape,
 )
+from torchstore_amd.ops.quant_row import (
+    RowQuantizedTensor,
+    alloc_row_quantized,
+    dequantize_fp8_row_into,
+    quantize_fp8_row,
+    row_scales_shape,
+)
 from torchstore_amd.utils.logging import LatencyTracker, get_logger
 
 logger = get_logger("torchstore_amd.state_dict")
@@ -71,7 +81,8 @@ MAPPING_KEY = "<MAPPING>"
 SCALES_KEY = "<FP8_SCALES>"
 MX_SCALES_KEY = "<MX_SCALES>"
 MX6_SCALES_KEY = "<MX6_SCALES>"
-_SCALES_KEYS = (SCALES_KEY, MX_SCALES_KEY, MX6_SCALES_KEY)
+ROW_SCALES_KEY = "<FP8_ROW_SCALES>"
+_SCALES_KEYS = (SCALES_KEY, MX_SCALES_KEY, MX6_SCALES_KEY, ROW_SCALES_KEY)
 
 
 def _selects(policy, flat_key: str, value: Any) -> bool:
@@ -127,13 +138,28 @@ class Mxfp6BlockQuant:
         return _selects(self, flat_key, value)
 
 
-_POLICIES = (Fp8BlockQuant, Mxfp4BlockQuant, Mxfp6BlockQuant)
-TransferQuant = Union[None, str, Fp8BlockQuant, Mxfp4BlockQuant, Mxfp6BlockQuant]
+@dataclass(frozen=True)
+class Fp8RowQuant:
+    """``transfer_quant`` policy: FP8 e4m3 with one f32 scale per row
+    (``ops/quant_row.py``), the operand layout of row-wise scaled FP8 GEMMs.
+    Selects entries by the same rule as :class:`Fp8BlockQuant`."""
+
+    min_numel: int = 0
+    exclude: Sequence[str] = ()
+
+    def selects(self, flat_key: str, value: Any) -> bool:
+        return _selects(self, flat_key, value)
+
+
+_POLICIES = (Fp8BlockQuant, Mxfp4BlockQuant, Mxfp6BlockQuant, Fp8RowQuant)
+TransferQuant = Union[
+    None, str, Fp8BlockQuant, Mxfp4BlockQuant, Mxfp6BlockQuant, Fp8RowQuant
+]
 
 
 def _resolve_quant(
     transfer_quant: TransferQuant,
-) -> Union[None, Fp8BlockQuant, Mxfp4BlockQuant, Mxfp6BlockQuant]:
+) -> Union[None, Fp8BlockQuant, Mxfp4BlockQuant, Mxfp6BlockQuant, Fp8RowQuant]:
     if transfer_quant is None or isinstance(transfer_quant, _POLICIES):
         return transfer_quant
     if transfer_quant == "fp8_e4m3":
@@ -142,11 +168,36 @@ def _resolve_quant(
         return Mxfp4BlockQuant()
     if transfer_quant == "mxfp6_e2m3":
         return Mxfp6BlockQuant()
+    if transfer_quant == "fp8_e4m3_row":
+        return Fp8RowQuant()
     raise ValueError(
         f"unknown transfer_quant {transfer_quant!r}: expected 'fp8_e4m3', "
-        "'mxfp4', 'mxfp6_e2m3', an Fp8BlockQuant, an Mxfp4BlockQuant or an "
-        "Mxfp6BlockQuant"
+        "'mxfp4', 'mxfp6_e2m3', 'fp8_e4m3_row', an Fp8BlockQuant, an "
+        "Mxfp4BlockQuant, an Mxfp6BlockQuant or an Fp8RowQuant"
     )
+
+
+@dataclass(frozen=True)
+class _Fp8Format:
+    """Where the two FP8 formats differ on this side of the store."""
+
+    field: str  # the QuantMapping attribute that lists its entries
+    scales_key: str
+    leaf: type  # the class of a quantised leaf
+    scales_shape: Callable  # payload shape -> scales shape
+    alloc: Callable
+    quantize: Callable
+    dequantize_into: Callable
+
+
+_FP8_BLOCK = _Fp8Format(
+    "quant", SCALES_KEY, QuantizedTensor, scales_shape, alloc_quantized,
+    quantize_fp8, dequantize_fp8_into,
+)
+_FP8_ROW = _Fp8Format(
+    "row", ROW_SCALES_KEY, RowQuantizedTensor, row_scales_shape,
+    alloc_row_quantized, quantize_fp8_row, dequantize_fp8_row_into,
+)
 
 
 @dataclass(frozen=True)
@@ -175,10 +226,11 @@ _MXFP6 = _MxFormat(
 
 class QuantMapping(dict):
     """The commit marker of a quantised push: the usual flat-key mapping plus
-    ``quant``, ``{flat_key: original dtype}`` of the FP8 entries, or ``mx``
-    / ``mx6``, ``{flat_key: (original dtype, logical shape)}`` of the MXFP4 /
-    MXFP6 ones.  A plain push keeps writing a plain dict, so readers tell
-    them apart from the marker they fetch anyway."""
+    ``quant`` or ``row``, ``{flat_key: original dtype}`` of the block-scaled
+    or row-scaled FP8 entries, or ``mx`` / ``mx6``, ``{flat_key: (original
+    dtype, logical shape)}`` of the MXFP4 / MXFP6 ones.  A plain push keeps
+    writing a plain dict, so readers tell them apart from the marker they
+    fetch anyway."""
 
     def __init__(
         self,
@@ -186,16 +238,23 @@ class QuantMapping(dict):
         quant: Optional[Dict[str, torch.dtype]] = None,
         mx: Optional[Dict[str, Tuple[torch.dtype, Tuple[int, ...]]]] = None,
         mx6: Optional[Dict[str, Tuple[torch.dtype, Tuple[int, ...]]]] = None,
+        row: Optional[Dict[str, torch.dtype]] = None,
     ):
         super().__init__(mapping)
         self.quant = dict(quant or {})
         self.mx = dict(mx or {})
         self.mx6 = dict(mx6 or {})
+        self.row = dict(row or {})
 
     def __reduce__(self):
         # a field is emitted only from the first format that needs it on, so
         # the marker of a plain, FP8 or MXFP4 push pickles as it did before
         # the later formats existed: byte-identical on the wire
+        if self.row:
+            return (
+                QuantMapping,
+                (dict(self), self.quant, self.mx, self.mx6, self.row),
+            )
         if self.mx6:
             return (QuantMapping, (dict(self), self.quant, self.mx, self.mx6))
         if not self.mx:
@@ -280,10 +339,13 @@ def _plan_quant_dests(
     user_flat: Dict[str, Any],
     quant: Dict[str, torch.dtype],
     fetches: Dict[str, Any],
+    fmt: _Fp8Format = _FP8_BLOCK,
 ) -> List[Tuple[Tuple[torch.Tensor, torch.Tensor], torch.Tensor]]:
-    """Point the fetches of quantised entries at FP8 destinations.
+    """Point the fetches of the entries ``quant`` of either FP8 format at FP8
+    destinations.
 
-    A ``QuantizedTensor`` leaf receives payload and scales in place.  A
+    A leaf of the format's own class (``QuantizedTensor``,
+    ``RowQuantizedTensor``) receives payload and scales in place.  A
     tensor leaf gets scratch buffers on its own device; the returned
     ``[((payload, scales), dest), ...]`` is what remains to dequantise once
     the fetches have landed.
@@ -294,15 +356,15 @@ def _plan_quant_dests(
     by_device: Dict[torch.device, List[str]] = {}
     for k in wanted:
         leaf = user_flat[k]
-        if isinstance(leaf, QuantizedTensor):
-            if tuple(leaf.scales.shape) != scales_shape(leaf.payload.shape):
+        if isinstance(leaf, fmt.leaf):
+            if tuple(leaf.scales.shape) != fmt.scales_shape(leaf.payload.shape):
                 raise ValueError(
-                    f"QuantizedTensor destination for {k!r}: scales shape "
+                    f"{fmt.leaf.__name__} destination for {k!r}: scales shape "
                     f"{tuple(leaf.scales.shape)} does not belong to a payload "
                     f"of shape {tuple(leaf.payload.shape)}"
                 )
             fetches[f"{key}/{k}"] = leaf.payload
-            fetches[f"{key}/{SCALES_KEY}/{k}"] = leaf.scales
+            fetches[f"{key}/{fmt.scales_key}/{k}"] = leaf.scales
         elif (
             type(leaf) is torch.Tensor
             and leaf.dtype in QUANT_DTYPES
@@ -312,15 +374,15 @@ def _plan_quant_dests(
         else:
             raise TypeError(
                 f"entry {k!r} was pushed quantised: its destination must be "
-                "a plain f32/bf16/f16 tensor or a QuantizedTensor, got "
+                f"a plain f32/bf16/f16 tensor or a {fmt.leaf.__name__}, got "
                 f"{type(leaf).__name__}"
             )
     pending = []
     for device, ks in by_device.items():
-        bufs = alloc_quantized([user_flat[k].shape for k in ks], device)
+        bufs = fmt.alloc([user_flat[k].shape for k in ks], device)
         for k, (payload, scales) in zip(ks, bufs):
             fetches[f"{key}/{k}"] = payload
-            fetches[f"{key}/{SCALES_KEY}/{k}"] = scales
+            fetches[f"{key}/{fmt.scales_key}/{k}"] = scales
             pending.append(((payload, scales), user_flat[k]))
     return pending
 
@@ -428,9 +490,11 @@ async def put_state_dict(
             entries = {k: (flat[k].dtype, tuple(flat[k].shape)) for k in qkeys}
             mapping = QuantMapping(mapping, **{fmt.field: entries})
         else:
-            scales_key = SCALES_KEY
-            pairs = dict(zip(qkeys, quantize_fp8([flat[k] for k in qkeys])))
-            mapping = QuantMapping(mapping, {k: flat[k].dtype for k in qkeys})
+            fp8 = _FP8_ROW if isinstance(quant, Fp8RowQuant) else _FP8_BLOCK
+            scales_key = fp8.scales_key
+            pairs = dict(zip(qkeys, fp8.quantize([flat[k] for k in qkeys])))
+            entries = {k: flat[k].dtype for k in qkeys}
+            mapping = QuantMapping(mapping, **{fp8.field: entries})
         rest = _cast_floating(
             {k: v for k, v in flat.items() if k not in pairs}, transfer_dtype
         )
@@ -469,12 +533,12 @@ async def get_state_dict(
 ) -> Dict[str, Any]:
     """``dequantize`` matters only for entries pushed with ``transfer_quant``
     and only when no ``user_state_dict`` is given: ``False`` returns them as
-    :class:`QuantizedTensor` (FP8), :class:`MxQuantizedTensor` (MXFP4) or
-    :class:`Mxfp6QuantizedTensor` (MXFP6) leaves instead of tensors of the
-    original dtype.  With a ``user_state_dict`` the destination leaf decides:
-    a tensor (f32/bf16/f16) is dequantised into, a ``QuantizedTensor`` /
-    ``MxQuantizedTensor`` / ``Mxfp6QuantizedTensor`` receives payload and
-    scales as stored."""
+    :class:`QuantizedTensor` (FP8), :class:`RowQuantizedTensor` (row-scaled
+    FP8), :class:`MxQuantizedTensor` (MXFP4) or :class:`Mxfp6QuantizedTensor`
+    (MXFP6) leaves instead of tensors of the original dtype.  With a
+    ``user_state_dict`` the destination leaf decides: a tensor (f32/bf16/f16)
+    is dequantised into, a leaf of the stored format's own class receives
+    payload and scales as stored."""
     direct = direct or direct_rdma
     if direct:
         from torchstore_amd.weight_sync import DirectWeightSyncDest
@@ -496,9 +560,11 @@ async def get_state_dict(
             f"no state_dict was pushed under {key!r} (missing commit marker)"
         ) from exc
     tracker.step("mapping")
-    # {flat_key: original dtype} of the quantised entries; empty for a
-    # plain push, and then everything below is what it always was
-    quant: Dict[str, torch.dtype] = getattr(mapping, "quant", {})
+    # {flat_key: original dtype} of the FP8 entries, with their format (a
+    # push uses one); empty for a plain push, and then everything below is
+    # what it always was
+    fp8 = _FP8_ROW if getattr(mapping, "row", None) else _FP8_BLOCK
+    quant: Dict[str, torch.dtype] = getattr(mapping, fp8.field, {})
     # {flat_key: (original dtype, logical shape)} of the MXFP4 or MXFP6
     # entries, with their format (a push uses one)
     mx_fmt = _MXFP6 if getattr(mapping, "mx6", None) else _MXFP4
@@ -523,7 +589,7 @@ async def get_state_dict(
                     f"stored-only entries {sorted(extra)[:5]}"
                 )
         fetches = {f"{key}/{k}": v for k, v in user_flat.items()}
-        pending = _plan_quant_dests(key, user_flat, quant, fetches)
+        pending = _plan_quant_dests(key, user_flat, quant, fetches, fp8)
         mx_pending = _plan_mx_dests(key, user_flat, mx, fetches, mx_fmt)
         if quant or mx:
             fetches = _scales_beside_payloads(fetches, key, user_flat)
@@ -545,7 +611,7 @@ async def get_state_dict(
         }
         if pending:
             # one batched dequant lands in the user's tensors in place
-            dequantize_fp8_into(
+            fp8.dequantize_into(
                 [pair for pair, _ in pending], [dst for _, dst in pending]
             )
             tracker.step("dequant")
@@ -562,7 +628,7 @@ async def get_state_dict(
     flat_keys = list(mapping.keys())
     fetches = {f"{key}/{k}": None for k in flat_keys}
     if quant:
-        fetches.update({f"{key}/{SCALES_KEY}/{k}": None for k in quant})
+        fetches.update({f"{key}/{fp8.scales_key}/{k}": None for k in quant})
         fetches = _scales_beside_payloads(fetches, key, flat_keys)
     if mx:
         fetches.update({f"{key}/{mx_fmt.scales_key}/{k}": None for k in mx})
@@ -580,9 +646,7 @@ async def get_state_dict(
     flat = {k: results[f"{key}/{k}"] for k in flat_keys}
     if quant:
         leaves = {
-            k: QuantizedTensor(
-                flat[k], results[f"{key}/{SCALES_KEY}/{k}"], dtype
-            )
+            k: fp8.leaf(flat[k], results[f"{key}/{fp8.scales_key}/{k}"], dtype)
             for k, dtype in quant.items()
         }
         if dequantize:
@@ -590,7 +654,7 @@ async def get_state_dict(
                 torch.empty(q.shape, dtype=q.orig_dtype, device=q.payload.device)
                 for q in leaves.values()
             ]
-            dequantize_fp8_into(
+            fp8.dequantize_into(
                 [(q.payload, q.scales) for q in leaves.values()], outs
             )
             flat.update(zip(leaves.keys(), outs))
