@@ -36,10 +36,12 @@ from torchstore_amd.ops.mx import MxQuantizedTensor
 from torchstore_amd.ops.mx6 import Mxfp6QuantizedTensor
 from torchstore_amd.ops.quant import QuantizedTensor
 from torchstore_amd.ops.quant_row import RowQuantizedTensor
+from torchstore_amd.ops.quant_tile import TileQuantizedTensor
 from torchstore_amd.spmd import SPMDEnv, initialize_spmd, shutdown_spmd
 from torchstore_amd.state_dict import (
     Fp8BlockQuant,
     Fp8RowQuant,
+    Fp8TileQuant,
     Mxfp4BlockQuant,
     Mxfp6BlockQuant,
 )
@@ -85,12 +87,14 @@ __all__ = [
     "TransportType",
     "Fp8BlockQuant",
     "Fp8RowQuant",
+    "Fp8TileQuant",
     "Mxfp4BlockQuant",
     "Mxfp6BlockQuant",
     "MxQuantizedTensor",
     "Mxfp6QuantizedTensor",
     "QuantizedTensor",
     "RowQuantizedTensor",
+    "TileQuantizedTensor",
     "LocalShard",
     "Request",
     "TensorSlice",

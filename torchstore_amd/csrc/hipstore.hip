@@ -35,6 +35,9 @@
 //   * quant_row_batch / dequant_row_batch (quant_row.h) — K10/K11: row-scaled
 //     FP8 (e4m3, one f32 scale per row: the operand of row-wise scaled GEMMs),
 //     a wave, a workgroup in registers or a workgroup streaming per row.
+//   * quant_tile_batch / dequant_tile_batch (quant_tile.h) — K12/K13:
+//     tile-scaled FP8 (e4m3, one f32 scale per 128 x 128 tile: the layout of
+//     block-FP8 weights), a workgroup holding a tile in registers.
 //   * host_register / host_unregister — pin SHM pages for DMA;
 //     clear_last_error — drop the code a failed pin made elsewhere left.
 // Underneath: plan.h turns the python tuples into descriptors (HIP-free; also
@@ -57,6 +60,7 @@
 #include "quant_mx.h"
 #include "quant_mx6.h"
 #include "quant_row.h"
+#include "quant_tile.h"
 
 #include <pybind11/pybind11.h>
 #include <pybind11/stl.h>
@@ -232,6 +236,24 @@ static std::pair<uint32_t, uint32_t> row_limits() {
   return {kRowWave, kRowWg};
 }
 
+// K12/K13; python passes per tensor:
+//   (wide_ptr, payload_ptr, scales_ptr, mats, rows, cols, wide_dtype)
+using PyTileItem = std::tuple<uintptr_t, uintptr_t, uintptr_t, uint64_t,
+                              uint64_t, uint64_t, int>;
+
+template <bool DEQUANT>
+static void quant_tile_batch(const std::vector<PyTileItem>& items, int device,
+                             uintptr_t stream_handle) {
+  std::vector<TileIn> in;
+  in.reserve(items.size());
+  for (const auto& it : items) {
+    const auto& [wide, payload, scales, mats, rows, cols, dtype] = it;
+    in.push_back(TileIn{wide, payload, scales, mats, rows, cols, dtype});
+  }
+  launch_quant_tile<DEQUANT>(plan_tile(in, DEQUANT), device,
+                             reinterpret_cast<hipStream_t>(stream_handle));
+}
+
 // host pinning and staging
 
 // single UVA-resolved copy on a dedicated pool stream (blocking).  Used by
@@ -336,6 +358,16 @@ PYBIND11_MODULE(_hipstore, m) {
     return g_row_launches.load(std::memory_order_relaxed);
   });
   m.def("row_limits", &row_limits);
+  // items: (wide_ptr, payload_ptr, scales_ptr, mats, rows, cols, wide_dtype)
+  m.def("quant_tile_batch", &quant_tile_batch<false>, py::arg("items"),
+        py::arg("device"), py::arg("stream"),
+        py::call_guard<py::gil_scoped_release>());
+  m.def("dequant_tile_batch", &quant_tile_batch<true>, py::arg("items"),
+        py::arg("device"), py::arg("stream"),
+        py::call_guard<py::gil_scoped_release>());
+  m.def("tile_launches", []() {
+    return g_tile_launches.load(std::memory_order_relaxed);
+  });
   m.def("sdma_copy", &sdma_copy, py::arg("dst"), py::arg("src"),
         py::arg("nbytes"), py::arg("device"),
         py::call_guard<py::gil_scoped_release>());

@@ -50,6 +50,15 @@ static constexpr uint32_t kRowWaveRows = 4;   // rows per unit, one per wave
 static constexpr uint32_t kRowDqPasses = 2;
 static constexpr uint32_t kRowDqUnitElems = kRowDqPasses * 256u * 16u;
 
+// Tile-scaled FP8 (K12/K13): one f32 scale per kTile x kTile tile of each
+// matrix of a stack [mats, rows, cols].  A quantise unit is one tile, which a
+// 256-thread workgroup holds in registers: 8 lanes per tile row, 32 rows per
+// pass, kTilePasses passes.  Dequantise is flat like K11.
+static constexpr uint32_t kTile = 128;
+static constexpr uint32_t kTilePasses = kTile / 32u;
+static constexpr uint32_t kTileDqPasses = 2;
+static constexpr uint32_t kTileDqUnitElems = kTileDqPasses * 256u * 16u;
+
 // descriptors (read by the kernels; every one carries the exclusive prefix
 // sum of units that unit_walk.h searches)
 
@@ -134,6 +143,24 @@ struct RowDesc {
 };
 static_assert(sizeof(RowDesc) == 64, "RowDesc is meant to be 64 bytes");
 
+// K12/K13: quantise unit = one tile, numbered like its scale, the tile column
+// fastest: unit = (mat * ntr + tile_row) * ntc + tile_col; dequantise unit =
+// kTileDqUnitElems consecutive elements
+struct TileDesc {
+  uintptr_t wide;         // f32/bf16/f16 tensor: quant source, dequant dest
+  uintptr_t payload;      // e4m3 bytes, same element order as `wide`
+  uintptr_t scales;       // f32 [mats, ntr, ntc]
+  uint64_t units_prefix;  // exclusive prefix sum of units
+  uint64_t numel;         // mats * rows * cols
+  uint32_t rows;          // of one matrix; mats * rows fits 32 bits
+  uint32_t cols;
+  uint32_t ntr;           // tile rows per matrix = ceil(rows / 128)
+  uint32_t ntc;           // tile columns = ceil(cols / 128)
+  uint32_t dtype;         // DType code of `wide` (0 = f32, 1 = f16, 2 = bf16)
+  uint32_t fast;          // 1 = 16B-vector path
+};
+static_assert(sizeof(TileDesc) == 64, "TileDesc is meant to be 64 bytes");
+
 template <typename Desc>
 struct Plan {
   std::vector<Desc> descs;
@@ -156,6 +183,13 @@ struct SliceIn {
 struct QuantIn {
   uintptr_t wide, payload, scales;
   uint64_t rows, cols;
+  int dtype;
+};
+
+// (wide_ptr, payload_ptr, scales_ptr, mats, rows, cols, wide_dtype)
+struct TileIn {
+  uintptr_t wide, payload, scales;
+  uint64_t mats, rows, cols;
   int dtype;
 };
 
@@ -323,6 +357,38 @@ inline Plan<RowDesc> plan_row(const std::vector<QuantIn>& in, bool dequant,
     else if (mode == kRowModeWave)
       p.units += (it.rows + kRowWaveRows - 1) / kRowWaveRows;
     else p.units += it.rows;
+  }
+  return p;
+}
+
+// Tile-scaled FP8 quant / dequant plan (scales: one f32 per 128 x 128 tile of
+// each of the `mats` matrices); tensors with no elements are dropped.  The
+// kernels take rows and columns in 32 bits, and the dequantise side numbers
+// the rows of the whole stack in 32 bits as well.
+inline Plan<TileDesc> plan_tile(const std::vector<TileIn>& in, bool dequant) {
+  Plan<TileDesc> p;
+  p.descs.reserve(in.size());
+  for (const TileIn& it : in) {
+    if (it.dtype < 0 || it.dtype > 2)
+      throw std::runtime_error("unsupported dtype");
+    if (it.mats == 0 || it.rows == 0 || it.cols == 0) continue;
+    if (it.cols > UINT32_MAX || it.rows > UINT32_MAX ||
+        it.mats > UINT32_MAX / it.rows)
+      throw std::runtime_error("tensor too large for one tile descriptor");
+    if (it.scales & 3u) throw std::runtime_error("scales must be 4B aligned");
+    const uint32_t es = it.dtype == 0 ? 4u : 2u;
+    if (it.wide % es) throw std::runtime_error("misaligned tensor");
+    const uint32_t fast =
+        (((it.wide | it.payload) & 15u) == 0 && (it.cols & 15u) == 0) ? 1u : 0u;
+    const uint64_t ntr = (it.rows + kTile - 1) / kTile;
+    const uint64_t ntc = (it.cols + kTile - 1) / kTile;
+    const uint64_t numel = it.mats * it.rows * it.cols;
+    p.descs.push_back(TileDesc{it.wide, it.payload, it.scales, p.units, numel,
+                               (uint32_t)it.rows, (uint32_t)it.cols,
+                               (uint32_t)ntr, (uint32_t)ntc,
+                               (uint32_t)it.dtype, fast});
+    if (dequant) p.units += (numel + kTileDqUnitElems - 1) / kTileDqUnitElems;
+    else p.units += it.mats * ntr * ntc;
   }
   return p;
 }

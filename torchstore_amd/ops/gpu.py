@@ -8,6 +8,7 @@ The extension is built in-tree for gfx950 (``python setup.py build_ext
 * K6/K7 batched MXFP4 (packed e2m1 + e8m0 block scales) kernels;
 * K8/K9 batched MXFP6 (packed e2m3, the same scales) kernels;
 * K10/K11 batched row-scaled FP8 (one f32 scale per row) kernels;
+* K12/K13 batched tile-scaled FP8 (one f32 scale per 128 x 128 tile) kernels;
 * HIP IPC: export/open ``hipIpcMemHandle_t``, batched peer copies on
   dedicated streams, event completion;
 * host page pinning (``hipHostRegister``) for the SHM transport.
@@ -214,6 +215,43 @@ def row_limits():
     work in K10, one of up to ``R`` stays in a workgroup's registers, and a
     longer one is streamed twice."""
     return tuple(ext().row_limits())
+
+
+def _tile_items(triples):
+    items = []
+    for wide, payload, scales in triples:
+        if not (
+            wide.is_contiguous()
+            and payload.is_contiguous()
+            and scales.is_contiguous()
+        ):
+            raise ValueError("fp8 tile quant kernels require contiguous tensors")
+        cols = wide.shape[-1]
+        rows = wide.shape[-2] if wide.dim() > 1 else 1
+        mats = wide.numel() // (rows * cols) if rows * cols else 0
+        items.append(
+            (wide.data_ptr(), payload.data_ptr(), scales.data_ptr(),
+             mats, rows, cols, _DTYPE_CODES[wide.dtype])
+        )
+    return items
+
+
+def quant_tile_batch(triples, device: torch.device) -> None:
+    """K12: ``[(src, payload, scales), ...]`` — tile-scaled FP8 quantise of N
+    tensors in ONE launch on the caller's current stream (async).  ``scales``
+    is the f32 buffer of ``ops.quant_tile.tile_scales_shape(src.shape)``."""
+    ext().quant_tile_batch(_tile_items(triples), device.index, _stream(device))
+
+
+def dequant_tile_batch(triples, device: torch.device) -> None:
+    """K13: ``[(dst, payload, scales), ...]`` — the mirror image of K12; the
+    destination dtype (f32/bf16/f16) decides the output rounding."""
+    ext().dequant_tile_batch(_tile_items(triples), device.index, _stream(device))
+
+
+def tile_launches() -> int:
+    """Launches of K12 + K13 so far (counted apart from the other formats)."""
+    return ext().tile_launches()
 
 
 # a contiguous source below this many bytes is ONE flat descriptor; the

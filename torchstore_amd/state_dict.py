@@ -27,7 +27,11 @@ MXFP6 (``ops/mx6.py``) in the same way: scales under
 ``"{key}/<MX6_SCALES>/{flat_key}"``, marker field ``mx6``.
 ``transfer_quant="fp8_e4m3_row"`` is FP8 with one scale per row
 (``ops/quant_row.py``): scales of shape ``[rows, 1]`` under
-``"{key}/<FP8_ROW_SCALES>/{flat_key}"``, marker field ``row``.  A push uses
+``"{key}/<FP8_ROW_SCALES>/{flat_key}"``, marker field ``row``.
+``transfer_quant="fp8_e4m3_tile"`` is FP8 with one scale per 128 x 128 tile
+(``ops/quant_tile.py``, the layout of block-FP8 weights): scales of shape
+``[*lead, ceil(R / 128), ceil(C / 128)]`` under
+``"{key}/<FP8_TILE_SCALES>/{flat_key}"``, marker field ``tile``.  A push uses
 one policy.
 """
 
@@ -71,6 +75,13 @@ from torchstore_amd.ops.quant_row import (
     quantize_fp8_row,
     row_scales_shape,
 )
+from torchstore_amd.ops.quant_tile import (
+    TileQuantizedTensor,
+    alloc_tile_quantized,
+    dequantize_fp8_tile_into,
+    quantize_fp8_tile,
+    tile_scales_shape,
+)
 from torchstore_amd.utils.logging import LatencyTracker, get_logger
 
 logger = get_logger("torchstore_amd.state_dict")
@@ -82,7 +93,10 @@ SCALES_KEY = "<FP8_SCALES>"
 MX_SCALES_KEY = "<MX_SCALES>"
 MX6_SCALES_KEY = "<MX6_SCALES>"
 ROW_SCALES_KEY = "<FP8_ROW_SCALES>"
-_SCALES_KEYS = (SCALES_KEY, MX_SCALES_KEY, MX6_SCALES_KEY, ROW_SCALES_KEY)
+TILE_SCALES_KEY = "<FP8_TILE_SCALES>"
+_SCALES_KEYS = (
+    SCALES_KEY, MX_SCALES_KEY, MX6_SCALES_KEY, ROW_SCALES_KEY, TILE_SCALES_KEY,
+)
 
 
 def _selects(policy, flat_key: str, value: Any) -> bool:
@@ -151,15 +165,34 @@ class Fp8RowQuant:
         return _selects(self, flat_key, value)
 
 
-_POLICIES = (Fp8BlockQuant, Mxfp4BlockQuant, Mxfp6BlockQuant, Fp8RowQuant)
+@dataclass(frozen=True)
+class Fp8TileQuant:
+    """``transfer_quant`` policy: FP8 e4m3 with one f32 scale per 128 x 128
+    tile (``ops/quant_tile.py``), the layout of block-FP8 weights.  Selects
+    entries by the same rule as :class:`Fp8BlockQuant`."""
+
+    min_numel: int = 0
+    exclude: Sequence[str] = ()
+
+    def selects(self, flat_key: str, value: Any) -> bool:
+        return _selects(self, flat_key, value)
+
+
+_POLICIES = (
+    Fp8BlockQuant, Mxfp4BlockQuant, Mxfp6BlockQuant, Fp8RowQuant, Fp8TileQuant,
+)
 TransferQuant = Union[
-    None, str, Fp8BlockQuant, Mxfp4BlockQuant, Mxfp6BlockQuant, Fp8RowQuant
+    None, str, Fp8BlockQuant, Mxfp4BlockQuant, Mxfp6BlockQuant, Fp8RowQuant,
+    Fp8TileQuant,
 ]
 
 
 def _resolve_quant(
     transfer_quant: TransferQuant,
-) -> Union[None, Fp8BlockQuant, Mxfp4BlockQuant, Mxfp6BlockQuant, Fp8RowQuant]:
+) -> Union[
+    None, Fp8BlockQuant, Mxfp4BlockQuant, Mxfp6BlockQuant, Fp8RowQuant,
+    Fp8TileQuant,
+]:
     if transfer_quant is None or isinstance(transfer_quant, _POLICIES):
         return transfer_quant
     if transfer_quant == "fp8_e4m3":
@@ -170,16 +203,19 @@ def _resolve_quant(
         return Mxfp6BlockQuant()
     if transfer_quant == "fp8_e4m3_row":
         return Fp8RowQuant()
+    if transfer_quant == "fp8_e4m3_tile":
+        return Fp8TileQuant()
     raise ValueError(
         f"unknown transfer_quant {transfer_quant!r}: expected 'fp8_e4m3', "
-        "'mxfp4', 'mxfp6_e2m3', 'fp8_e4m3_row', an Fp8BlockQuant, an "
-        "Mxfp4BlockQuant, an Mxfp6BlockQuant or an Fp8RowQuant"
+        "'mxfp4', 'mxfp6_e2m3', 'fp8_e4m3_row', 'fp8_e4m3_tile', an "
+        "Fp8BlockQuant, an Mxfp4BlockQuant, an Mxfp6BlockQuant, an Fp8RowQuant "
+        "or an Fp8TileQuant"
     )
 
 
 @dataclass(frozen=True)
 class _Fp8Format:
-    """Where the two FP8 formats differ on this side of the store."""
+    """Where the FP8 formats differ on this side of the store."""
 
     field: str  # the QuantMapping attribute that lists its entries
     scales_key: str
@@ -198,6 +234,13 @@ _FP8_ROW = _Fp8Format(
     "row", ROW_SCALES_KEY, RowQuantizedTensor, row_scales_shape,
     alloc_row_quantized, quantize_fp8_row, dequantize_fp8_row_into,
 )
+_FP8_TILE = _Fp8Format(
+    "tile", TILE_SCALES_KEY, TileQuantizedTensor, tile_scales_shape,
+    alloc_tile_quantized, quantize_fp8_tile, dequantize_fp8_tile_into,
+)
+_FP8_BY_POLICY = {
+    Fp8BlockQuant: _FP8_BLOCK, Fp8RowQuant: _FP8_ROW, Fp8TileQuant: _FP8_TILE,
+}
 
 
 @dataclass(frozen=True)
@@ -226,9 +269,9 @@ _MXFP6 = _MxFormat(
 
 class QuantMapping(dict):
     """The commit marker of a quantised push: the usual flat-key mapping plus
-    ``quant`` or ``row``, ``{flat_key: original dtype}`` of the block-scaled
-    or row-scaled FP8 entries, or ``mx`` / ``mx6``, ``{flat_key: (original
-    dtype, logical shape)}`` of the MXFP4 / MXFP6 ones.  A plain push keeps
+    ``quant``, ``row`` or ``tile``, ``{flat_key: original dtype}`` of the
+    block-scaled, row-scaled or tile-scaled FP8 entries, or ``mx`` / ``mx6``,
+    ``{flat_key: (original dtype, logical shape)}`` of the MXFP4 / MXFP6 ones.  A plain push keeps
     writing a plain dict, so readers tell them apart from the marker they
     fetch anyway."""
 
@@ -239,17 +282,24 @@ class QuantMapping(dict):
         mx: Optional[Dict[str, Tuple[torch.dtype, Tuple[int, ...]]]] = None,
         mx6: Optional[Dict[str, Tuple[torch.dtype, Tuple[int, ...]]]] = None,
         row: Optional[Dict[str, torch.dtype]] = None,
+        tile: Optional[Dict[str, torch.dtype]] = None,
     ):
         super().__init__(mapping)
         self.quant = dict(quant or {})
         self.mx = dict(mx or {})
         self.mx6 = dict(mx6 or {})
         self.row = dict(row or {})
+        self.tile = dict(tile or {})
 
     def __reduce__(self):
         # a field is emitted only from the first format that needs it on, so
         # the marker of a plain, FP8 or MXFP4 push pickles as it did before
         # the later formats existed: byte-identical on the wire
+        if self.tile:
+            return (
+                QuantMapping,
+                (dict(self), self.quant, self.mx, self.mx6, self.row, self.tile),
+            )
         if self.row:
             return (
                 QuantMapping,
@@ -345,7 +395,7 @@ def _plan_quant_dests(
     destinations.
 
     A leaf of the format's own class (``QuantizedTensor``,
-    ``RowQuantizedTensor``) receives payload and scales in place.  A
+    ``RowQuantizedTensor``, ``TileQuantizedTensor``) receives payload and scales in place.  A
     tensor leaf gets scratch buffers on its own device; the returned
     ``[((payload, scales), dest), ...]`` is what remains to dequantise once
     the fetches have landed.
@@ -490,7 +540,7 @@ async def put_state_dict(
             entries = {k: (flat[k].dtype, tuple(flat[k].shape)) for k in qkeys}
             mapping = QuantMapping(mapping, **{fmt.field: entries})
         else:
-            fp8 = _FP8_ROW if isinstance(quant, Fp8RowQuant) else _FP8_BLOCK
+            fp8 = _FP8_BY_POLICY[type(quant)]
             scales_key = fp8.scales_key
             pairs = dict(zip(qkeys, fp8.quantize([flat[k] for k in qkeys])))
             entries = {k: flat[k].dtype for k in qkeys}
@@ -534,7 +584,8 @@ async def get_state_dict(
     """``dequantize`` matters only for entries pushed with ``transfer_quant``
     and only when no ``user_state_dict`` is given: ``False`` returns them as
     :class:`QuantizedTensor` (FP8), :class:`RowQuantizedTensor` (row-scaled
-    FP8), :class:`MxQuantizedTensor` (MXFP4) or :class:`Mxfp6QuantizedTensor`
+    FP8), :class:`TileQuantizedTensor` (tile-scaled FP8),
+    :class:`MxQuantizedTensor` (MXFP4) or :class:`Mxfp6QuantizedTensor`
     (MXFP6) leaves instead of tensors of the original dtype.  With a
     ``user_state_dict`` the destination leaf decides: a tensor (f32/bf16/f16)
     is dequantised into, a leaf of the stored format's own class receives
@@ -563,7 +614,10 @@ async def get_state_dict(
     # {flat_key: original dtype} of the FP8 entries, with their format (a
     # push uses one); empty for a plain push, and then everything below is
     # what it always was
-    fp8 = _FP8_ROW if getattr(mapping, "row", None) else _FP8_BLOCK
+    fp8 = next(
+        (f for f in (_FP8_TILE, _FP8_ROW) if getattr(mapping, f.field, None)),
+        _FP8_BLOCK,
+    )
     quant: Dict[str, torch.dtype] = getattr(mapping, fp8.field, {})
     # {flat_key: (original dtype, logical shape)} of the MXFP4 or MXFP6
     # entries, with their format (a push uses one)
