@@ -36,11 +36,13 @@ from torchstore_amd.ops.mx import MxQuantizedTensor
 from torchstore_amd.ops.mx6 import Mxfp6QuantizedTensor
 from torchstore_amd.ops.quant import QuantizedTensor
 from torchstore_amd.ops.quant_row import RowQuantizedTensor
+from torchstore_amd.ops.quant_tensor import TensorQuantizedTensor
 from torchstore_amd.ops.quant_tile import TileQuantizedTensor
 from torchstore_amd.spmd import SPMDEnv, initialize_spmd, shutdown_spmd
 from torchstore_amd.state_dict import (
     Fp8BlockQuant,
     Fp8RowQuant,
+    Fp8TensorQuant,
     Fp8TileQuant,
     Mxfp4BlockQuant,
     Mxfp6BlockQuant,
@@ -88,6 +90,7 @@ __all__ = [
     "Fp8BlockQuant",
     "Fp8RowQuant",
     "Fp8TileQuant",
+    "Fp8TensorQuant",
     "Mxfp4BlockQuant",
     "Mxfp6BlockQuant",
     "MxQuantizedTensor",
@@ -95,6 +98,7 @@ __all__ = [
     "QuantizedTensor",
     "RowQuantizedTensor",
     "TileQuantizedTensor",
+    "TensorQuantizedTensor",
     "LocalShard",
     "Request",
     "TensorSlice",

@@ -47,6 +47,8 @@
 //   HIPSTORE_MX6_GRID     65536                  >= 64
 //   HIPSTORE_ROW_GRID     65536                  >= 64
 //   HIPSTORE_TILE_GRID    65536                  >= 64
+//   HIPSTORE_TENSOR_GRID  8192 quantise,         >= 64
+//                         65536 dequantise
 //   HIPSTORE_ROW_WAVE     4096                   <= 4096: longest row a wave
 //                                                takes (row-scaled FP8)
 //   HIPSTORE_ROW_WG       16384                  <= 16384: longest row a

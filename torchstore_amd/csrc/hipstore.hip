@@ -38,6 +38,10 @@
 //   * quant_tile_batch / dequant_tile_batch (quant_tile.h) — K12/K13:
 //     tile-scaled FP8 (e4m3, one f32 scale per 128 x 128 tile: the layout of
 //     block-FP8 weights), a workgroup holding a tile in registers.
+//   * quant_tensor_batch / dequant_tensor_batch (quant_tensor.h) — K14/K15:
+//     per-tensor FP8 (e4m3, one f32 scale per matrix: the usual FP8
+//     checkpoint format), the amax of a matrix travelling through memory
+//     between two launches.
 //   * host_register / host_unregister — pin SHM pages for DMA;
 //     clear_last_error — drop the code a failed pin made elsewhere left.
 // Underneath: plan.h turns the python tuples into descriptors (HIP-free; also
@@ -60,6 +64,7 @@
 #include "quant_mx.h"
 #include "quant_mx6.h"
 #include "quant_row.h"
+#include "quant_tensor.h"
 #include "quant_tile.h"
 
 #include <pybind11/pybind11.h>
@@ -254,6 +259,25 @@ static void quant_tile_batch(const std::vector<PyTileItem>& items, int device,
                              reinterpret_cast<hipStream_t>(stream_handle));
 }
 
+// K14/K15; python passes per tensor:
+//   (wide_ptr, payload_ptr, scales_ptr, amax_ptr, mats, rows, cols, wide_dtype)
+// amax_ptr: one zeroed u32 per matrix on the quantise side, 0 on the other
+using PyTensorItem = std::tuple<uintptr_t, uintptr_t, uintptr_t, uintptr_t,
+                                uint64_t, uint64_t, uint64_t, int>;
+
+template <bool DEQUANT>
+static void quant_tensor_batch(const std::vector<PyTensorItem>& items,
+                               int device, uintptr_t stream_handle) {
+  std::vector<TensorIn> in;
+  in.reserve(items.size());
+  for (const auto& it : items) {
+    const auto& [wide, payload, scales, amax, mats, rows, cols, dtype] = it;
+    in.push_back(TensorIn{wide, payload, scales, amax, mats, rows, cols, dtype});
+  }
+  launch_quant_tensor<DEQUANT>(plan_tensor(in, DEQUANT), device,
+                               reinterpret_cast<hipStream_t>(stream_handle));
+}
+
 // host pinning and staging
 
 // single UVA-resolved copy on a dedicated pool stream (blocking).  Used by
@@ -367,6 +391,17 @@ PYBIND11_MODULE(_hipstore, m) {
         py::call_guard<py::gil_scoped_release>());
   m.def("tile_launches", []() {
     return g_tile_launches.load(std::memory_order_relaxed);
+  });
+  // items: (wide_ptr, payload_ptr, scales_ptr, amax_ptr, mats, rows, cols,
+  // wide_dtype); the quantise is two launches, the dequantise one
+  m.def("quant_tensor_batch", &quant_tensor_batch<false>, py::arg("items"),
+        py::arg("device"), py::arg("stream"),
+        py::call_guard<py::gil_scoped_release>());
+  m.def("dequant_tensor_batch", &quant_tensor_batch<true>, py::arg("items"),
+        py::arg("device"), py::arg("stream"),
+        py::call_guard<py::gil_scoped_release>());
+  m.def("tensor_launches", []() {
+    return g_tensor_launches.load(std::memory_order_relaxed);
   });
   m.def("sdma_copy", &sdma_copy, py::arg("dst"), py::arg("src"),
         py::arg("nbytes"), py::arg("device"),

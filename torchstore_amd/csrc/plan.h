@@ -59,6 +59,19 @@ static constexpr uint32_t kTilePasses = kTile / 32u;
 static constexpr uint32_t kTileDqPasses = 2;
 static constexpr uint32_t kTileDqUnitElems = kTileDqPasses * 256u * 16u;
 
+// Per-tensor FP8 (K14/K15): one f32 scale per matrix of a stack [mats, rows,
+// cols].  A quantise unit is a run of up to kTensorUnitElems elements that
+// lies inside ONE matrix (kTensorPasses passes of 256 lanes x 16 elements),
+// counted per matrix, so a unit never straddles two scales; both quantise
+// launches walk the same units.  Dequantise is flat like K13.
+static constexpr uint32_t kTensorPasses = 4;
+static constexpr uint32_t kTensorUnitElems = kTensorPasses * 256u * 16u;
+static constexpr uint32_t kTensorDqPasses = 2;
+static constexpr uint32_t kTensorDqUnitElems = kTensorDqPasses * 256u * 16u;
+// largest tensor of one descriptor: byte offsets of an f32 tensor stay below
+// 2^49 and no product of the planner or the kernels leaves 64 bits
+static constexpr uint64_t kTensorMaxElems = 1ull << 47;
+
 // descriptors (read by the kernels; every one carries the exclusive prefix
 // sum of units that unit_walk.h searches)
 
@@ -161,6 +174,24 @@ struct TileDesc {
 };
 static_assert(sizeof(TileDesc) == 64, "TileDesc is meant to be 64 bytes");
 
+// K14/K15: quantise unit = the run [u * kTensorUnitElems, ...) of matrix
+// `mat`, unit = mat * units_per_mat + u; dequantise unit = kTensorDqUnitElems
+// consecutive elements of the whole tensor
+struct TensorDesc {
+  uintptr_t wide;          // f32/bf16/f16 tensor: quant source, dequant dest
+  uintptr_t payload;       // e4m3 bytes, same element order as `wide`
+  uintptr_t scales;        // f32 [mats]
+  uintptr_t amax;          // u32 [mats]: bit patterns of the matrices' amax,
+                           // zeroed before the quantise; 0 on the dequant side
+  uint64_t units_prefix;   // exclusive prefix sum of units
+  uint64_t numel;          // mats * mat_elems
+  uint64_t mat_elems;      // rows * cols of one matrix
+  uint64_t units_per_mat;  // quantise units of one matrix
+  uint32_t dtype;          // DType code of `wide` (0 = f32, 1 = f16, 2 = bf16)
+  uint32_t fast;           // 1 = 16B-vector path
+};
+static_assert(sizeof(TensorDesc) == 72, "TensorDesc is meant to be 72 bytes");
+
 template <typename Desc>
 struct Plan {
   std::vector<Desc> descs;
@@ -189,6 +220,13 @@ struct QuantIn {
 // (wide_ptr, payload_ptr, scales_ptr, mats, rows, cols, wide_dtype)
 struct TileIn {
   uintptr_t wide, payload, scales;
+  uint64_t mats, rows, cols;
+  int dtype;
+};
+
+// (wide_ptr, payload_ptr, scales_ptr, amax_ptr, mats, rows, cols, wide_dtype)
+struct TensorIn {
+  uintptr_t wide, payload, scales, amax;
   uint64_t mats, rows, cols;
   int dtype;
 };
@@ -389,6 +427,44 @@ inline Plan<TileDesc> plan_tile(const std::vector<TileIn>& in, bool dequant) {
                                (uint32_t)it.dtype, fast});
     if (dequant) p.units += (numel + kTileDqUnitElems - 1) / kTileDqUnitElems;
     else p.units += it.mats * ntr * ntc;
+  }
+  return p;
+}
+
+// Per-tensor FP8 quant / dequant plan (scales: one f32 per matrix of the
+// `mats` matrices); tensors with no elements are dropped.  A tensor of more
+// than kTensorMaxElems = 2^47 elements is refused.  Fast needs both bases 16B
+// aligned and whole 16-element chunks per matrix, so no chunk straddles two
+// scales; for a single matrix that is numel % 16 == 0.  The quantise side
+// needs the amax slots (one zeroed u32 per matrix, apart from `scales`).
+inline Plan<TensorDesc> plan_tensor(const std::vector<TensorIn>& in,
+                                    bool dequant) {
+  Plan<TensorDesc> p;
+  p.descs.reserve(in.size());
+  for (const TensorIn& it : in) {
+    if (it.dtype < 0 || it.dtype > 2)
+      throw std::runtime_error("unsupported dtype");
+    if (it.mats == 0 || it.rows == 0 || it.cols == 0) continue;
+    if (it.rows > kTensorMaxElems / it.cols ||
+        it.mats > kTensorMaxElems / (it.rows * it.cols))
+      throw std::runtime_error("tensor too large for one tensor descriptor");
+    if (it.scales & 3u) throw std::runtime_error("scales must be 4B aligned");
+    if (!dequant && (it.amax == 0 || (it.amax & 3u)))
+      throw std::runtime_error("amax slots must be given and 4B aligned");
+    const uint32_t es = it.dtype == 0 ? 4u : 2u;
+    if (it.wide % es) throw std::runtime_error("misaligned tensor");
+    const uint64_t mat_elems = it.rows * it.cols;
+    const uint64_t numel = it.mats * mat_elems;
+    const uint32_t fast =
+        (((it.wide | it.payload) & 15u) == 0 && (mat_elems & 15u) == 0) ? 1u
+                                                                        : 0u;
+    const uint64_t upm = (mat_elems + kTensorUnitElems - 1) / kTensorUnitElems;
+    p.descs.push_back(TensorDesc{it.wide, it.payload, it.scales,
+                                 dequant ? 0 : it.amax, p.units, numel,
+                                 mat_elems, upm, (uint32_t)it.dtype, fast});
+    if (dequant)
+      p.units += (numel + kTensorDqUnitElems - 1) / kTensorDqUnitElems;
+    else p.units += it.mats * upm;
   }
   return p;
 }

@@ -9,6 +9,7 @@ The extension is built in-tree for gfx950 (``python setup.py build_ext
 * K8/K9 batched MXFP6 (packed e2m3, the same scales) kernels;
 * K10/K11 batched row-scaled FP8 (one f32 scale per row) kernels;
 * K12/K13 batched tile-scaled FP8 (one f32 scale per 128 x 128 tile) kernels;
+* K14/K15 batched per-tensor FP8 (one f32 scale per matrix) kernels;
 * HIP IPC: export/open ``hipIpcMemHandle_t``, batched peer copies on
   dedicated streams, event completion;
 * host page pinning (``hipHostRegister``) for the SHM transport.
@@ -252,6 +253,65 @@ def dequant_tile_batch(triples, device: torch.device) -> None:
 def tile_launches() -> int:
     """Launches of K12 + K13 so far (counted apart from the other formats)."""
     return ext().tile_launches()
+
+
+def _stack_dims(wide):
+    cols = wide.shape[-1]
+    rows = wide.shape[-2] if wide.dim() > 1 else 1
+    return (wide.numel() // (rows * cols) if rows * cols else 0), rows, cols
+
+
+def _tensor_items(triples, amax_slots=None):
+    """Items of K14/K15; ``amax_slots``, one int32 per matrix of the batch,
+    is cut up between the tensors in order (quantise side only)."""
+    items = []
+    slot = 0
+    for wide, payload, scales in triples:
+        if not (
+            wide.is_contiguous()
+            and payload.is_contiguous()
+            and scales.is_contiguous()
+        ):
+            raise ValueError("fp8 tensor quant kernels require contiguous tensors")
+        mats, rows, cols = _stack_dims(wide)
+        if mats and scales.numel() != mats:
+            raise ValueError("fp8 tensor quant: one scale per matrix expected")
+        amax = 0 if amax_slots is None else amax_slots.data_ptr() + 4 * slot
+        slot += mats
+        items.append(
+            (wide.data_ptr(), payload.data_ptr(), scales.data_ptr(), amax,
+             mats, rows, cols, _DTYPE_CODES[wide.dtype])
+        )
+    return items
+
+
+def quant_tensor_batch(triples, device: torch.device) -> None:
+    """K14: ``[(src, payload, scales), ...]`` — per-tensor FP8 quantise of N
+    tensors in TWO launches on the caller's current stream (async): the first
+    leaves every matrix's amax in a slot of its own, the second converts.
+    ``scales`` is the f32 buffer of
+    ``ops.quant_tensor.tensor_scales_shape(src.shape)``.  The slots are
+    scratch of this call, apart from ``scales`` and zeroed on the same stream
+    ahead of the launches."""
+    nmats = sum(_stack_dims(wide)[0] for wide, _, _ in triples)
+    amax_slots = torch.zeros(max(nmats, 1), dtype=torch.int32, device=device)
+    ext().quant_tensor_batch(
+        _tensor_items(triples, amax_slots), device.index, _stream(device)
+    )
+
+
+def dequant_tensor_batch(triples, device: torch.device) -> None:
+    """K15: ``[(dst, payload, scales), ...]`` — the mirror image of K14 in one
+    launch; the destination dtype (f32/bf16/f16) decides the output rounding."""
+    ext().dequant_tensor_batch(
+        _tensor_items(triples), device.index, _stream(device)
+    )
+
+
+def tensor_launches() -> int:
+    """Launches of K14 + K15 so far (counted apart from the other formats): a
+    quantise call adds 2, a dequantise call 1."""
+    return ext().tensor_launches()
 
 
 # a contiguous source below this many bytes is ONE flat descriptor; the

@@ -31,8 +31,11 @@ MXFP6 (``ops/mx6.py``) in the same way: scales under
 ``transfer_quant="fp8_e4m3_tile"`` is FP8 with one scale per 128 x 128 tile
 (``ops/quant_tile.py``, the layout of block-FP8 weights): scales of shape
 ``[*lead, ceil(R / 128), ceil(C / 128)]`` under
-``"{key}/<FP8_TILE_SCALES>/{flat_key}"``, marker field ``tile``.  A push uses
-one policy.
+``"{key}/<FP8_TILE_SCALES>/{flat_key}"``, marker field ``tile``.
+``transfer_quant="fp8_e4m3_tensor"`` is FP8 with one scale per matrix
+(``ops/quant_tensor.py``, the usual FP8 checkpoint format): scales of shape
+``[*lead, 1, 1]`` under ``"{key}/<FP8_TENSOR_SCALES>/{flat_key}"``, marker
+field ``whole``.  A push uses one policy.
 """
 
 from __future__ import annotations
@@ -75,6 +78,13 @@ from torchstore_amd.ops.quant_row import (
     quantize_fp8_row,
     row_scales_shape,
 )
+from torchstore_amd.ops.quant_tensor import (
+    TensorQuantizedTensor,
+    alloc_tensor_quantized,
+    dequantize_fp8_tensor_into,
+    quantize_fp8_tensor,
+    tensor_scales_shape,
+)
 from torchstore_amd.ops.quant_tile import (
     TileQuantizedTensor,
     alloc_tile_quantized,
@@ -94,8 +104,10 @@ MX_SCALES_KEY = "<MX_SCALES>"
 MX6_SCALES_KEY = "<MX6_SCALES>"
 ROW_SCALES_KEY = "<FP8_ROW_SCALES>"
 TILE_SCALES_KEY = "<FP8_TILE_SCALES>"
+TENSOR_SCALES_KEY = "<FP8_TENSOR_SCALES>"
 _SCALES_KEYS = (
     SCALES_KEY, MX_SCALES_KEY, MX6_SCALES_KEY, ROW_SCALES_KEY, TILE_SCALES_KEY,
+    TENSOR_SCALES_KEY,
 )
 
 
@@ -178,12 +190,27 @@ class Fp8TileQuant:
         return _selects(self, flat_key, value)
 
 
+@dataclass(frozen=True)
+class Fp8TensorQuant:
+    """``transfer_quant`` policy: FP8 e4m3 with one f32 scale per matrix
+    (``ops/quant_tensor.py``), the format of FP8 checkpoints with one
+    ``weight_scale`` per weight or per expert.  Selects entries by the same
+    rule as :class:`Fp8BlockQuant`."""
+
+    min_numel: int = 0
+    exclude: Sequence[str] = ()
+
+    def selects(self, flat_key: str, value: Any) -> bool:
+        return _selects(self, flat_key, value)
+
+
 _POLICIES = (
     Fp8BlockQuant, Mxfp4BlockQuant, Mxfp6BlockQuant, Fp8RowQuant, Fp8TileQuant,
+    Fp8TensorQuant,
 )
 TransferQuant = Union[
     None, str, Fp8BlockQuant, Mxfp4BlockQuant, Mxfp6BlockQuant, Fp8RowQuant,
-    Fp8TileQuant,
+    Fp8TileQuant, Fp8TensorQuant,
 ]
 
 
@@ -191,7 +218,7 @@ def _resolve_quant(
     transfer_quant: TransferQuant,
 ) -> Union[
     None, Fp8BlockQuant, Mxfp4BlockQuant, Mxfp6BlockQuant, Fp8RowQuant,
-    Fp8TileQuant,
+    Fp8TileQuant, Fp8TensorQuant,
 ]:
     if transfer_quant is None or isinstance(transfer_quant, _POLICIES):
         return transfer_quant
@@ -205,11 +232,13 @@ def _resolve_quant(
         return Fp8RowQuant()
     if transfer_quant == "fp8_e4m3_tile":
         return Fp8TileQuant()
+    if transfer_quant == "fp8_e4m3_tensor":
+        return Fp8TensorQuant()
     raise ValueError(
         f"unknown transfer_quant {transfer_quant!r}: expected 'fp8_e4m3', "
-        "'mxfp4', 'mxfp6_e2m3', 'fp8_e4m3_row', 'fp8_e4m3_tile', an "
-        "Fp8BlockQuant, an Mxfp4BlockQuant, an Mxfp6BlockQuant, an Fp8RowQuant "
-        "or an Fp8TileQuant"
+        "'mxfp4', 'mxfp6_e2m3', 'fp8_e4m3_row', 'fp8_e4m3_tile', "
+        "'fp8_e4m3_tensor', an Fp8BlockQuant, an Mxfp4BlockQuant, an "
+        "Mxfp6BlockQuant, an Fp8RowQuant, an Fp8TileQuant or an Fp8TensorQuant"
     )
 
 
@@ -238,8 +267,13 @@ _FP8_TILE = _Fp8Format(
     "tile", TILE_SCALES_KEY, TileQuantizedTensor, tile_scales_shape,
     alloc_tile_quantized, quantize_fp8_tile, dequantize_fp8_tile_into,
 )
+_FP8_TENSOR = _Fp8Format(
+    "whole", TENSOR_SCALES_KEY, TensorQuantizedTensor, tensor_scales_shape,
+    alloc_tensor_quantized, quantize_fp8_tensor, dequantize_fp8_tensor_into,
+)
 _FP8_BY_POLICY = {
     Fp8BlockQuant: _FP8_BLOCK, Fp8RowQuant: _FP8_ROW, Fp8TileQuant: _FP8_TILE,
+    Fp8TensorQuant: _FP8_TENSOR,
 }
 
 
@@ -269,8 +303,9 @@ _MXFP6 = _MxFormat(
 
 class QuantMapping(dict):
     """The commit marker of a quantised push: the usual flat-key mapping plus
-    ``quant``, ``row`` or ``tile``, ``{flat_key: original dtype}`` of the
-    block-scaled, row-scaled or tile-scaled FP8 entries, or ``mx`` / ``mx6``,
+    ``quant``, ``row``, ``tile`` or ``whole``, ``{flat_key: original dtype}``
+    of the block-scaled, row-scaled, tile-scaled or per-tensor FP8 entries, or
+    ``mx`` / ``mx6``,
     ``{flat_key: (original dtype, logical shape)}`` of the MXFP4 / MXFP6 ones.  A plain push keeps
     writing a plain dict, so readers tell them apart from the marker they
     fetch anyway."""
@@ -283,6 +318,7 @@ class QuantMapping(dict):
         mx6: Optional[Dict[str, Tuple[torch.dtype, Tuple[int, ...]]]] = None,
         row: Optional[Dict[str, torch.dtype]] = None,
         tile: Optional[Dict[str, torch.dtype]] = None,
+        whole: Optional[Dict[str, torch.dtype]] = None,
     ):
         super().__init__(mapping)
         self.quant = dict(quant or {})
@@ -290,11 +326,18 @@ class QuantMapping(dict):
         self.mx6 = dict(mx6 or {})
         self.row = dict(row or {})
         self.tile = dict(tile or {})
+        self.whole = dict(whole or {})
 
     def __reduce__(self):
         # a field is emitted only from the first format that needs it on, so
         # the marker of a plain, FP8 or MXFP4 push pickles as it did before
         # the later formats existed: byte-identical on the wire
+        if self.whole:
+            return (
+                QuantMapping,
+                (dict(self), self.quant, self.mx, self.mx6, self.row,
+                 self.tile, self.whole),
+            )
         if self.tile:
             return (
                 QuantMapping,
@@ -395,7 +438,8 @@ def _plan_quant_dests(
     destinations.
 
     A leaf of the format's own class (``QuantizedTensor``,
-    ``RowQuantizedTensor``, ``TileQuantizedTensor``) receives payload and scales in place.  A
+    ``RowQuantizedTensor``, ``TileQuantizedTensor``,
+    ``TensorQuantizedTensor``) receives payload and scales in place.  A
     tensor leaf gets scratch buffers on its own device; the returned
     ``[((payload, scales), dest), ...]`` is what remains to dequantise once
     the fetches have landed.
@@ -585,6 +629,7 @@ async def get_state_dict(
     and only when no ``user_state_dict`` is given: ``False`` returns them as
     :class:`QuantizedTensor` (FP8), :class:`RowQuantizedTensor` (row-scaled
     FP8), :class:`TileQuantizedTensor` (tile-scaled FP8),
+    :class:`TensorQuantizedTensor` (per-tensor FP8),
     :class:`MxQuantizedTensor` (MXFP4) or :class:`Mxfp6QuantizedTensor`
     (MXFP6) leaves instead of tensors of the original dtype.  With a
     ``user_state_dict`` the destination leaf decides: a tensor (f32/bf16/f16)
@@ -615,7 +660,10 @@ async def get_state_dict(
     # push uses one); empty for a plain push, and then everything below is
     # what it always was
     fp8 = next(
-        (f for f in (_FP8_TILE, _FP8_ROW) if getattr(mapping, f.field, None)),
+        (
+            f for f in (_FP8_TENSOR, _FP8_TILE, _FP8_ROW)
+            if getattr(mapping, f.field, None)
+        ),
         _FP8_BLOCK,
     )
     quant: Dict[str, torch.dtype] = getattr(mapping, fp8.field, {})
