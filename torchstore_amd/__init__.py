@@ -34,6 +34,7 @@ from torchstore_amd.api import (
 )
 from torchstore_amd.ops.mx import MxQuantizedTensor
 from torchstore_amd.ops.mx6 import Mxfp6QuantizedTensor
+from torchstore_amd.ops.mx8 import Mxfp8QuantizedTensor
 from torchstore_amd.ops.quant import QuantizedTensor
 from torchstore_amd.ops.quant_row import RowQuantizedTensor
 from torchstore_amd.ops.quant_tensor import TensorQuantizedTensor
@@ -46,6 +47,7 @@ from torchstore_amd.state_dict import (
     Fp8TileQuant,
     Mxfp4BlockQuant,
     Mxfp6BlockQuant,
+    Mxfp8BlockQuant,
 )
 from torchstore_amd.strategy import (
     HostStrategy,
@@ -93,8 +95,10 @@ __all__ = [
     "Fp8TensorQuant",
     "Mxfp4BlockQuant",
     "Mxfp6BlockQuant",
+    "Mxfp8BlockQuant",
     "MxQuantizedTensor",
     "Mxfp6QuantizedTensor",
+    "Mxfp8QuantizedTensor",
     "QuantizedTensor",
     "RowQuantizedTensor",
     "TileQuantizedTensor",

@@ -45,6 +45,7 @@
 //   HIPSTORE_QUANT_GRID   65536                  >= 64
 //   HIPSTORE_MX_GRID      65536                  >= 64
 //   HIPSTORE_MX6_GRID     65536                  >= 64
+//   HIPSTORE_MX8_GRID     65536                  >= 64
 //   HIPSTORE_ROW_GRID     65536                  >= 64
 //   HIPSTORE_TILE_GRID    65536                  >= 64
 //   HIPSTORE_TENSOR_GRID  8192 quantise,         >= 64

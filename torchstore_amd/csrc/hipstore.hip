@@ -42,6 +42,11 @@
 //     per-tensor FP8 (e4m3, one f32 scale per matrix: the usual FP8
 //     checkpoint format), the amax of a matrix travelling through memory
 //     between two launches.
+//   * quant_mx8_batch / dequant_mx8_batch (quant_mx8.h) — K16/K17: MXFP8
+//     (OCP e4m3 values, the blocks, scales, descriptors and plan of MXFP4:
+//     the 8-bit operand of gfx950's scaled matrix instructions), one 16B
+//     payload access per lane, dequantised by the scaled conversion
+//     instruction, with a launch counter of their own.
 //   * host_register / host_unregister — pin SHM pages for DMA;
 //     clear_last_error — drop the code a failed pin made elsewhere left.
 // Underneath: plan.h turns the python tuples into descriptors (HIP-free; also
@@ -63,6 +68,7 @@
 #include "quant_fp8.h"
 #include "quant_mx.h"
 #include "quant_mx6.h"
+#include "quant_mx8.h"
 #include "quant_row.h"
 #include "quant_tensor.h"
 #include "quant_tile.h"
@@ -220,6 +226,21 @@ static void quant_mx6_batch(const std::vector<PyQuantItem>& items, int device,
                             reinterpret_cast<hipStream_t>(stream_handle));
 }
 
+// K16/K17; the same tuples and plan, the payload being one e4m3 byte per
+// element
+template <bool DEQUANT>
+static void quant_mx8_batch(const std::vector<PyQuantItem>& items, int device,
+                            uintptr_t stream_handle) {
+  std::vector<QuantIn> in;
+  in.reserve(items.size());
+  for (const auto& it : items) {
+    const auto& [wide, payload, scales, rows, cols, dtype] = it;
+    in.push_back(QuantIn{wide, payload, scales, rows, cols, dtype});
+  }
+  launch_quant_mx8<DEQUANT>(plan_mx(in), device,
+                            reinterpret_cast<hipStream_t>(stream_handle));
+}
+
 // K10/K11; the same tuples, scales being one f32 per row.  The regime limits
 // default to what the kernels can hold (row_limits) and can only be lowered
 template <bool DEQUANT>
@@ -372,6 +393,15 @@ PYBIND11_MODULE(_hipstore, m) {
     return g_mx6_launches.load(std::memory_order_relaxed);
   });
   m.attr("MX6_LDS") = kMx6Lds;
+  m.def("quant_mx8_batch", &quant_mx8_batch<false>, py::arg("items"),
+        py::arg("device"), py::arg("stream"),
+        py::call_guard<py::gil_scoped_release>());
+  m.def("dequant_mx8_batch", &quant_mx8_batch<true>, py::arg("items"),
+        py::arg("device"), py::arg("stream"),
+        py::call_guard<py::gil_scoped_release>());
+  m.def("mx8_launches", []() {
+    return g_mx8_launches.load(std::memory_order_relaxed);
+  });
   m.def("quant_row_batch", &quant_row_batch<false>, py::arg("items"),
         py::arg("device"), py::arg("stream"),
         py::call_guard<py::gil_scoped_release>());

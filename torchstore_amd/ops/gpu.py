@@ -7,6 +7,7 @@ The extension is built in-tree for gfx950 (``python setup.py build_ext
 * K4/K5 batched block-scaled FP8 quantise / dequantise kernels;
 * K6/K7 batched MXFP4 (packed e2m1 + e8m0 block scales) kernels;
 * K8/K9 batched MXFP6 (packed e2m3, the same scales) kernels;
+* K16/K17 batched MXFP8 (e4m3 values, the scales of MXFP4) kernels;
 * K10/K11 batched row-scaled FP8 (one f32 scale per row) kernels;
 * K12/K13 batched tile-scaled FP8 (one f32 scale per 128 x 128 tile) kernels;
 * K14/K15 batched per-tensor FP8 (one f32 scale per matrix) kernels;
@@ -187,6 +188,29 @@ def dequant_mx6_batch(triples, device: torch.device) -> None:
 def mx6_launches() -> int:
     """Launches of K8 + K9 so far (counted apart from K4/K5 and K6/K7)."""
     return ext().mx6_launches()
+
+
+def quant_mx8_batch(triples, device: torch.device) -> None:
+    """K16: ``[(src, payload, scales), ...]`` — MXFP8 quantise of N tensors
+    in ONE launch on the caller's current stream (async).  ``payload`` is the
+    float8_e4m3fn buffer of the source's shape, ``scales`` the uint8 buffer
+    of ``ops.mx8.mx8_scales_shape(src.shape)``."""
+    ext().quant_mx8_batch(
+        _quant_items(triples, "mxfp8"), device.index, _stream(device)
+    )
+
+
+def dequant_mx8_batch(triples, device: torch.device) -> None:
+    """K17: ``[(dst, payload, scales), ...]`` — the mirror image of K16; the
+    destination dtype (f32/bf16/f16) decides the output rounding."""
+    ext().dequant_mx8_batch(
+        _quant_items(triples, "mxfp8"), device.index, _stream(device)
+    )
+
+
+def mx8_launches() -> int:
+    """Launches of K16 + K17 so far (counted apart from the other formats)."""
+    return ext().mx8_launches()
 
 
 def quant_row_batch(triples, device: torch.device) -> None:

@@ -35,7 +35,11 @@ MXFP6 (``ops/mx6.py``) in the same way: scales under
 ``transfer_quant="fp8_e4m3_tensor"`` is FP8 with one scale per matrix
 (``ops/quant_tensor.py``, the usual FP8 checkpoint format): scales of shape
 ``[*lead, 1, 1]`` under ``"{key}/<FP8_TENSOR_SCALES>/{flat_key}"``, marker
-field ``whole``.  A push uses one policy.
+field ``whole``.  ``transfer_quant="mxfp8_e4m3"`` is MXFP8 (``ops/mx8.py``:
+e4m3 values in the source's shape, one e8m0 scale byte per block of 32):
+scales of shape ``[*shape[:-1], ceil(cols / 32)]`` under
+``"{key}/<MX8_SCALES>/{flat_key}"``, marker field ``mx8``.  A push uses one
+policy.
 """
 
 from __future__ import annotations
@@ -62,6 +66,13 @@ from torchstore_amd.ops.mx6 import (
     dequantize_mxfp6_into,
     mx6_shapes,
     quantize_mxfp6,
+)
+from torchstore_amd.ops.mx8 import (
+    Mxfp8QuantizedTensor,
+    alloc_mx8,
+    dequantize_mxfp8_into,
+    mx8_scales_shape,
+    quantize_mxfp8,
 )
 from torchstore_amd.ops.quant import (
     QUANT_DTYPES,
@@ -105,9 +116,10 @@ MX6_SCALES_KEY = "<MX6_SCALES>"
 ROW_SCALES_KEY = "<FP8_ROW_SCALES>"
 TILE_SCALES_KEY = "<FP8_TILE_SCALES>"
 TENSOR_SCALES_KEY = "<FP8_TENSOR_SCALES>"
+MX8_SCALES_KEY = "<MX8_SCALES>"
 _SCALES_KEYS = (
     SCALES_KEY, MX_SCALES_KEY, MX6_SCALES_KEY, ROW_SCALES_KEY, TILE_SCALES_KEY,
-    TENSOR_SCALES_KEY,
+    TENSOR_SCALES_KEY, MX8_SCALES_KEY,
 )
 
 
@@ -204,13 +216,27 @@ class Fp8TensorQuant:
         return _selects(self, flat_key, value)
 
 
+@dataclass(frozen=True)
+class Mxfp8BlockQuant:
+    """``transfer_quant`` policy: MXFP8, e4m3 values with one e8m0 scale byte
+    per block of 32 (``ops/mx8.py``), the 8-bit operand of the scaled matrix
+    instructions.  Selects entries by the same rule as
+    :class:`Fp8BlockQuant`."""
+
+    min_numel: int = 0
+    exclude: Sequence[str] = ()
+
+    def selects(self, flat_key: str, value: Any) -> bool:
+        return _selects(self, flat_key, value)
+
+
 _POLICIES = (
     Fp8BlockQuant, Mxfp4BlockQuant, Mxfp6BlockQuant, Fp8RowQuant, Fp8TileQuant,
-    Fp8TensorQuant,
+    Fp8TensorQuant, Mxfp8BlockQuant,
 )
 TransferQuant = Union[
     None, str, Fp8BlockQuant, Mxfp4BlockQuant, Mxfp6BlockQuant, Fp8RowQuant,
-    Fp8TileQuant, Fp8TensorQuant,
+    Fp8TileQuant, Fp8TensorQuant, Mxfp8BlockQuant,
 ]
 
 
@@ -218,7 +244,7 @@ def _resolve_quant(
     transfer_quant: TransferQuant,
 ) -> Union[
     None, Fp8BlockQuant, Mxfp4BlockQuant, Mxfp6BlockQuant, Fp8RowQuant,
-    Fp8TileQuant, Fp8TensorQuant,
+    Fp8TileQuant, Fp8TensorQuant, Mxfp8BlockQuant,
 ]:
     if transfer_quant is None or isinstance(transfer_quant, _POLICIES):
         return transfer_quant
@@ -234,11 +260,14 @@ def _resolve_quant(
         return Fp8TileQuant()
     if transfer_quant == "fp8_e4m3_tensor":
         return Fp8TensorQuant()
+    if transfer_quant == "mxfp8_e4m3":
+        return Mxfp8BlockQuant()
     raise ValueError(
         f"unknown transfer_quant {transfer_quant!r}: expected 'fp8_e4m3', "
         "'mxfp4', 'mxfp6_e2m3', 'fp8_e4m3_row', 'fp8_e4m3_tile', "
-        "'fp8_e4m3_tensor', an Fp8BlockQuant, an Mxfp4BlockQuant, an "
-        "Mxfp6BlockQuant, an Fp8RowQuant, an Fp8TileQuant or an Fp8TensorQuant"
+        "'fp8_e4m3_tensor', 'mxfp8_e4m3', an Fp8BlockQuant, an "
+        "Mxfp4BlockQuant, an Mxfp6BlockQuant, an Fp8RowQuant, an Fp8TileQuant, "
+        "an Fp8TensorQuant or an Mxfp8BlockQuant"
     )
 
 
@@ -271,9 +300,15 @@ _FP8_TENSOR = _Fp8Format(
     "whole", TENSOR_SCALES_KEY, TensorQuantizedTensor, tensor_scales_shape,
     alloc_tensor_quantized, quantize_fp8_tensor, dequantize_fp8_tensor_into,
 )
+# MXFP8 is an FP8 format on this side of the store: the payload has the
+# source's shape, so the marker needs the original dtype only
+_MX8 = _Fp8Format(
+    "mx8", MX8_SCALES_KEY, Mxfp8QuantizedTensor, mx8_scales_shape, alloc_mx8,
+    quantize_mxfp8, dequantize_mxfp8_into,
+)
 _FP8_BY_POLICY = {
     Fp8BlockQuant: _FP8_BLOCK, Fp8RowQuant: _FP8_ROW, Fp8TileQuant: _FP8_TILE,
-    Fp8TensorQuant: _FP8_TENSOR,
+    Fp8TensorQuant: _FP8_TENSOR, Mxfp8BlockQuant: _MX8,
 }
 
 
@@ -303,9 +338,9 @@ _MXFP6 = _MxFormat(
 
 class QuantMapping(dict):
     """The commit marker of a quantised push: the usual flat-key mapping plus
-    ``quant``, ``row``, ``tile`` or ``whole``, ``{flat_key: original dtype}``
-    of the block-scaled, row-scaled, tile-scaled or per-tensor FP8 entries, or
-    ``mx`` / ``mx6``,
+    ``quant``, ``row``, ``tile``, ``whole`` or ``mx8``, ``{flat_key: original
+    dtype}`` of the block-scaled, row-scaled, tile-scaled or per-tensor FP8
+    entries or the MXFP8 ones, or ``mx`` / ``mx6``,
     ``{flat_key: (original dtype, logical shape)}`` of the MXFP4 / MXFP6 ones.  A plain push keeps
     writing a plain dict, so readers tell them apart from the marker they
     fetch anyway."""
@@ -319,6 +354,7 @@ class QuantMapping(dict):
         row: Optional[Dict[str, torch.dtype]] = None,
         tile: Optional[Dict[str, torch.dtype]] = None,
         whole: Optional[Dict[str, torch.dtype]] = None,
+        mx8: Optional[Dict[str, torch.dtype]] = None,
     ):
         super().__init__(mapping)
         self.quant = dict(quant or {})
@@ -327,11 +363,18 @@ class QuantMapping(dict):
         self.row = dict(row or {})
         self.tile = dict(tile or {})
         self.whole = dict(whole or {})
+        self.mx8 = dict(mx8 or {})
 
     def __reduce__(self):
         # a field is emitted only from the first format that needs it on, so
         # the marker of a plain, FP8 or MXFP4 push pickles as it did before
         # the later formats existed: byte-identical on the wire
+        if self.mx8:
+            return (
+                QuantMapping,
+                (dict(self), self.quant, self.mx, self.mx6, self.row,
+                 self.tile, self.whole, self.mx8),
+            )
         if self.whole:
             return (
                 QuantMapping,
@@ -439,7 +482,8 @@ def _plan_quant_dests(
 
     A leaf of the format's own class (``QuantizedTensor``,
     ``RowQuantizedTensor``, ``TileQuantizedTensor``,
-    ``TensorQuantizedTensor``) receives payload and scales in place.  A
+    ``TensorQuantizedTensor``, ``Mxfp8QuantizedTensor``) receives payload and
+    scales in place.  A
     tensor leaf gets scratch buffers on its own device; the returned
     ``[((payload, scales), dest), ...]`` is what remains to dequantise once
     the fetches have landed.
@@ -630,8 +674,8 @@ async def get_state_dict(
     :class:`QuantizedTensor` (FP8), :class:`RowQuantizedTensor` (row-scaled
     FP8), :class:`TileQuantizedTensor` (tile-scaled FP8),
     :class:`TensorQuantizedTensor` (per-tensor FP8),
-    :class:`MxQuantizedTensor` (MXFP4) or :class:`Mxfp6QuantizedTensor`
-    (MXFP6) leaves instead of tensors of the original dtype.  With a
+    :class:`MxQuantizedTensor` (MXFP4), :class:`Mxfp6QuantizedTensor`
+    (MXFP6) or :class:`Mxfp8QuantizedTensor` (MXFP8) leaves instead of tensors of the original dtype.  With a
     ``user_state_dict`` the destination leaf decides: a tensor (f32/bf16/f16)
     is dequantised into, a leaf of the stored format's own class receives
     payload and scales as stored."""
@@ -661,7 +705,7 @@ async def get_state_dict(
     # what it always was
     fp8 = next(
         (
-            f for f in (_FP8_TENSOR, _FP8_TILE, _FP8_ROW)
+            f for f in (_MX8, _FP8_TENSOR, _FP8_TILE, _FP8_ROW)
             if getattr(mapping, f.field, None)
         ),
         _FP8_BLOCK,
